@@ -25,6 +25,15 @@ non-zero exit; `--allow-replicas` turns that into N independent copies
 (labelled in `parallelism` and `note`).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3_1M] [--scaling weak|strong]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(`value`, `ms_per_step`, the workload, the last step's CG iterations).
+`--dump-outputs DIR` also writes what the last timed step computed as
+DIR/<name>.npy.  `--full` adds every other measurement after the timed
+region: the phase split, the SpMV / iteration roofline, the Jacobi, SSOR and
+ICC legs, the 40-step runs and the CPU baselines (`--no-cpu`, `--no-jacobi`
+and `--no-full-run` drop single legs of it).
 
 Prints ONE JSON line on rank 0.
 """
@@ -81,7 +90,16 @@ def parse(argv=None):
                          "network's seams), -1 the engine's automatic choice")
     ap.add_argument("--no-jacobi", action="store_true",
                     help="skip the Jacobi-PCG leg (SURVEY §8d's iteration metric) after the timed steps")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's results (displacement, stress, active, reaction "
+                         "force, active count) as DIR/<name>.npy after the timed steps")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the phase split, the roofline, the Jacobi / "
+                         "SSOR / ICC legs, the 40-step runs and the CPU baselines")
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 def amg_iteration_bytes(ai, compact=None):
@@ -261,6 +279,26 @@ def full_run_reference(opts, fs, device):
                                 "PNG plots included); results/sim_20251117_181147_cpp/fea_results/"
                                 "solve_runtime_1.txt (solve_system + K@U per step, 40 steps)"}
     return r
+
+
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all files together
+
+
+def dump_outputs(path, arrays):
+    """Write each array as path/<name>.npy in float64.  Above DUMP_MAX_BYTES in
+    all, every array larger than an equal share of the budget is cut to a
+    fixed sample of its entries (seeded by the array's length alone, sorted
+    indices), so that two runs with the same arguments write the same entries."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64).ravel() for k, v in arrays.items()}
+    if sum(v.nbytes for v in arrays.values()) > DUMP_MAX_BYTES:
+        share = (DUMP_MAX_BYTES - 128 * len(arrays)) // (8 * len(arrays))  # entries per file, header aside
+        for k, v in arrays.items():
+            if v.size > share:
+                idx = np.sort(np.random.default_rng(v.size).choice(v.size, size=share, replace=False))
+                arrays[k] = v[idx]
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 def cpu_model():
@@ -549,6 +587,75 @@ def main(argv=None):
     job_dof = n_dof * (world if mode == "replicas" else 1)
 
     force, n_active, st = stats[-1]
+    iters = st.iters
+    nf = info["n_free_nodes"]
+    if a.dump_outputs:
+        # what the last timed step left on the engine (partitioned: the whole
+        # network's, gathered on rank 0 — collective)
+        if mode == "partitioned":
+            U, S, A = eng.gather_results()
+        else:
+            U, S, A = eng.displacement(), eng.stress(), eng.active()
+        if rank == 0:
+            dump_outputs(a.dump_outputs, {"displacement": U, "stress": S, "active": A,
+                                          "reaction_force": [force], "n_active": [n_active]})
+
+    parallelism = {"1gpu": "1gpu", "parts": f"parts{a.parts}@1gpu",
+                   "partitioned": f"partitioned{world} (RCCL)", "replicas": f"replicas{world}"}[mode]
+    workload = (f"{a.config}: {nx}x{ny} tiles, {n_dof} DOF, {st.n_free} free DOF, {len(e2n)} elements, "
+                f"load step {a.load_step}/40")
+    if mode == "partitioned":
+        workload += f", cut into {world} strips (min-cut grid, one per GPU; {a.scaling} scaling)"
+    elif mode == "parts":
+        workload += f", {a.parts} partitions on 1 GPU"
+    elif mode == "replicas":
+        workload += f", one copy per GPU ({world} GPUs)"
+    out = {
+        "metric": "DOF solved/sec + CG iters to 1e-8; SpMV achieved HBM GB/s vs roofline",
+        "value": job_dof * a.steps / dt,
+        "unit": "DOF/s",
+        "n_gpus": world,
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "ms_per_step": 1e3 * dt / a.steps,
+        "higher_is_better": True,
+        "scaling": a.scaling if mode == "partitioned" else "weak",
+        "vs_baseline": None,
+        "dtype": "f64" if pc != PC_GAMG else "f64 (CG; f32 AMG V-cycle)",
+        "data": "synthetic (tiled copies of results/sim_20251117_181147; no RNG)",
+        "config": {
+            "workload": workload,
+            "n_dof": n_dof, "n_free_dof": st.n_free, "n_elems": len(e2n),
+            "precond": a.precond, "rtol": a.rtol, "parallelism": parallelism,
+            "cg_kernel": "lanes" if info["cg_lanes"] else "sell", "n_lanes": info["n_lanes"],
+            "lane_geometry": {"block": info["block_size"], "grid": info["grid"], "halo_records": "compact" if info["halo_compact"] else "per lane"},
+            "rank0_part": {"free_dof": 3 * nf, "n_pairs": info["n_pairs"], "n_ghost": info["n_ghost"]},
+        },
+        "cg_iters": iters,
+        "relres": st.relres,
+    }
+    if mode in ("partitioned", "parts") and pc == PC_GAMG:
+        ch = eng.get_option("amg_dist_chosen")
+        how = ("option amg_dist -1: the faster of the two, measured in warmup" if a.amg_dist < 0
+               else f"--amg-dist {a.amg_dist}")
+        out["config"]["amg_partitions"] = {
+            0: "block Jacobi over per-partition hierarchies",
+            1: "distributed V-cycle of one global hierarchy (compact: level 0 split, levels below replicated)",
+            -1: "undecided"}[ch] + f" ({how})"
+    if note:
+        out["note"] = note
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        eng.close()
+        if dist is not None:
+            dist.destroy_process_group()
+
+    if not a.full:  # a plain run ends here: the headline figure alone
+        return finish()
+
+    # ---- --full: every other measurement, after the timed region
     # the phase split (mfea_stats t_*_ms) from one more step with the phase
     # events on (option phase_times; off in the timed steps: each event
     # between two kernels idles the GPU for several µs)
@@ -557,14 +664,12 @@ def main(argv=None):
     eng.set_option("phase_times", 0)
     ph_ms = {f: float(np.median([getattr(x, f) for x in ph]))
              for f in ("t_assemble_ms", "t_rhs_ms", "t_solve_ms", "t_post_ms", "t_setup_ms")}
-    iters = st.iters
     # ---- roofline, live HIP events on the engine's stream, algorithmic bytes
     # per launch as in DESIGN.md §4 (partitioned: rank 0's partition, without
     # exchange).  GAMG: `roofline` = the SpMV kernel w = A_0 u (f64, with the
     # CG's four partial sums — the metric's SpMV and the iteration's longest
     # launch), `roofline_iteration` = one whole PCG iteration (every launch).
     # Jacobi: the one fused iteration kernel.
-    nf = info["n_free_nodes"]
     tj = {}
     a.traffic = a.traffic or os.path.join(REPO, "profiles", f"traffic_{a.config}.json")
     if os.path.exists(a.traffic) and mode == "1gpu":
@@ -613,54 +718,20 @@ def main(argv=None):
         iter_traffic = None
     achieved = kernel_bytes / (kernel_ms * 1e-3) / 1e9
 
-    parallelism = {"1gpu": "1gpu", "parts": f"parts{a.parts}@1gpu",
-                   "partitioned": f"partitioned{world} (RCCL)", "replicas": f"replicas{world}"}[mode]
-    workload = (f"{a.config}: {nx}x{ny} tiles, {n_dof} DOF, {st.n_free} free DOF, {len(e2n)} elements, "
-                f"load step {a.load_step}/40")
-    if mode == "partitioned":
-        workload += f", cut into {world} strips (min-cut grid, one per GPU; {a.scaling} scaling)"
-    elif mode == "parts":
-        workload += f", {a.parts} partitions on 1 GPU"
-    elif mode == "replicas":
-        workload += f", one copy per GPU ({world} GPUs)"
-    out = {
-        "metric": "DOF solved/sec + CG iters to 1e-8; SpMV achieved HBM GB/s vs roofline",
-        "value": job_dof * a.steps / dt,
-        "unit": "DOF/s",
-        "n_gpus": world,
-        "steps": a.steps,
-        "warmup": a.warmup,
-        "ms_per_step": 1e3 * dt / a.steps,
-        "higher_is_better": True,
-        "scaling": a.scaling if mode == "partitioned" else "weak",
-        "vs_baseline": None,
-        "dtype": "f64" if pc != PC_GAMG else "f64 (CG; f32 AMG V-cycle)",
-        "data": "synthetic (tiled copies of results/sim_20251117_181147; no RNG)",
-        "config": {
-            "workload": workload,
-            "n_dof": n_dof, "n_free_dof": st.n_free, "n_elems": len(e2n),
-            "precond": a.precond, "rtol": a.rtol, "parallelism": parallelism,
-            "cg_kernel": "lanes" if info["cg_lanes"] else "sell", "n_lanes": info["n_lanes"],
-            "lane_geometry": {"block": info["block_size"], "grid": info["grid"], "halo_records": "compact" if info["halo_compact"] else "per lane"},
-            "rank0_part": {"free_dof": 3 * nf, "n_pairs": info["n_pairs"], "n_ghost": info["n_ghost"]},
-        },
-        "cg_iters": iters,
-        "relres": st.relres,
-        "step_breakdown_ms": {"assemble": ph_ms["t_assemble_ms"], "rhs": ph_ms["t_rhs_ms"],
-                              "pcg": ph_ms["t_solve_ms"], "post": ph_ms["t_post_ms"],
-                              "amg_setup (inside pcg)": ph_ms["t_setup_ms"],
-                              "note": "medians of 5 untimed steps with the phase events on"},
-        "roofline": {
-            "kernel": kernel,
-            "bound": "hbm",
-            "achieved": achieved,
-            "peak": PEAK_HBM_GBPS,
-            "unit": "GB/s",
-            "frac": achieved / PEAK_HBM_GBPS,
-            "traffic": traffic,
-            "alg_bytes_per_launch": kernel_bytes,
-            "avg_launch_us": kernel_ms * 1e3,
-        },
+    out["step_breakdown_ms"] = {"assemble": ph_ms["t_assemble_ms"], "rhs": ph_ms["t_rhs_ms"],
+                                "pcg": ph_ms["t_solve_ms"], "post": ph_ms["t_post_ms"],
+                                "amg_setup (inside pcg)": ph_ms["t_setup_ms"],
+                                "note": "medians of 5 untimed steps with the phase events on"}
+    out["roofline"] = {
+        "kernel": kernel,
+        "bound": "hbm",
+        "achieved": achieved,
+        "peak": PEAK_HBM_GBPS,
+        "unit": "GB/s",
+        "frac": achieved / PEAK_HBM_GBPS,
+        "traffic": traffic,
+        "alg_bytes_per_launch": kernel_bytes,
+        "avg_launch_us": kernel_ms * 1e3,
     }
     if split:
         out["roofline"]["note"] = ("rank 0's w = A_0 u over its own rows; bytes = the whole A_0's scaled by "
@@ -674,16 +745,6 @@ def main(argv=None):
     if pc == PC_GAMG:
         out["amg"] = {"levels": ai["levels"], "rows": ai["rows"], "blocks": ai["blocks"],
                       "setup_pair_items": ai["pair_items"], "split_levels": ai["n_dist"]}
-    if mode in ("partitioned", "parts") and pc == PC_GAMG:
-        ch = eng.get_option("amg_dist_chosen")
-        how = ("option amg_dist -1: the faster of the two, measured in warmup" if a.amg_dist < 0
-               else f"--amg-dist {a.amg_dist}")
-        out["config"]["amg_partitions"] = {
-            0: "block Jacobi over per-partition hierarchies",
-            1: "distributed V-cycle of one global hierarchy (compact: level 0 split, levels below replicated)",
-            -1: "undecided"}[ch] + f" ({how})"
-    if note:
-        out["note"] = note
 
     # ---- legs after the timed region (not part of `value`)
     if not a.no_jacobi and pc == PC_GAMG:
@@ -733,11 +794,7 @@ def main(argv=None):
     if rank == 0 and not a.no_cpu and world == 1:
         cpu_legs(a, out, xyz, e2n, top, bot, dy, n_dof)
 
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    eng.close()
-    if dist is not None:
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

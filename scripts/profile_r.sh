@@ -8,7 +8,7 @@ D=gpurun_out/prof_$TAG
 mkdir -p $D
 # rocprofv3 traces the hipGraph-replayed kernels too (no MFEA_NO_GRAPH: eager
 # launches under the profiler inflate a 6 µs kernel's duration by ≈ 1.5 µs)
-B="python3 bench.py --config $CFG --steps 1 --warmup 0 --no-cpu"
+B="python3 bench.py --full --config $CFG --steps 1 --warmup 0 --no-cpu"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $D/trace -o t -- $B > $D/trace.log 2>&1 || exit $?
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $D/fetch -o f -- $B > $D/fetch.log 2>&1 || exit $?
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $D/write -o w -- $B > $D/write.log 2>&1 || exit $?

@@ -137,6 +137,38 @@ def test_bench_gpus2_without_gpu_exits_nonzero():
     assert "partitioned solve failed" in r.stderr
 
 
+def test_plain_run_is_the_default_and_full_is_opt_in(bench):
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    a = bench.parse(["--full", "--no-cpu", "--dump-outputs", "d"])
+    assert a.full and a.no_cpu and a.dump_outputs == "d"
+    with pytest.raises(SystemExit):      # no timed step, no ms_per_step
+        bench.parse(["--steps", "0"])
+
+
+def test_dump_outputs_float64_files_and_fixed_sample(bench, tmp_path, monkeypatch):
+    import numpy as np
+    U = np.linspace(-1.0, 1.0, 3001)
+    arrays = {"displacement": U, "active": np.arange(500) % 3 == 0, "reaction_force": [2.5]}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    assert sorted(os.listdir(tmp_path / "a")) == ["active.npy", "displacement.npy", "reaction_force.npy"]
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in arrays}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert np.array_equal(got["displacement"], U) and got["reaction_force"].tolist() == [2.5]
+    assert np.array_equal(got["active"], (np.arange(500) % 3 == 0).astype(float))
+    # over the budget: arrays above an equal share are cut to the same sorted
+    # sample of their entries in every run, small ones stay whole
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 16384)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    files = [tmp_path / "b" / f for f in os.listdir(tmp_path / "b")]
+    assert sum(os.path.getsize(f) for f in files) <= 16384
+    b, c = (np.load(tmp_path / d / "displacement.npy") for d in ("b", "c"))
+    assert np.array_equal(b, c) and 0 < b.size < U.size
+    assert np.all(np.diff(b) > 0) and np.all(np.isin(b, U))
+    assert np.array_equal(np.load(tmp_path / "b" / "active.npy"), got["active"])
+
+
 def test_new_set_steps_label_the_step_after_the_failures(bench):
     """eng.step reports the active count after its own failure update, so the
     step that RUNS on a new set is the one after the count moved (round-5's
