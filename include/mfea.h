@@ -159,6 +159,51 @@ int mfea_get_displacement(mfea_handle* h, double* U /* 3·n_nodes, interleaved x
 int mfea_get_stress(mfea_handle* h, double* stress /* n_elems */);
 int mfea_get_active(mfea_handle* h, uint8_t* active /* n_elems */);
 
+/* ---- the whole load-step run (one call, records gathered on the device) ----- */
+/* The step loop of the drivers (src/fea_solver.py:229-285, src/fea_petsc.cpp:
+ * 270-406) as one call: n_steps times mfea_step(h, dy_top[k], dy_bot[k], opts,
+ * max_strain, ...) — the same internals, so every option, captured graph and
+ * kept-hierarchy rule acts as in a caller's loop — each followed by that
+ * step's record rows: what mfea_get_displacement / mfea_get_stress /
+ * mfea_get_active would return right after it (U with the grips' prescribed
+ * values, stress of the elements active at step start, activity AFTER the
+ * step's failures).  A kernel on the handle's stream gathers the rows in
+ * original node / element order into one of two device staging slabs; a
+ * second stream copies slab k&1 into row k of the caller's arrays while step
+ * k+1 computes (the arrays are page-locked with hipHostRegister for the
+ * call's duration; where that fails the copies go through two pinned host
+ * slabs and a host memcpy — read-only option "run_direct" tells which ran).
+ * Starts from the handle's current active set (no mfea_set_active).
+ *   - a solver failure at step k (MFEA_EMAXIT / MFEA_EBREAKDOWN) ends the run:
+ *     returns 0, *stop_reason = that code, *n_done = k; step k's rows are not
+ *     written (the drivers' `break` on LinAlgError, src/fea_solver.py:250-254);
+ *   - n_active == 0 after step k ends the run after recording it:
+ *     *stop_reason = MFEA_RUN_NO_ACTIVE, *n_done = k + 1 (src/fea_solver.py:283-285);
+ *   - any other error is returned as mfea_step returns it (*n_done = the
+ *     steps completed and recorded before it).
+ * On return every row < *n_done of every non-NULL record is complete in host
+ * memory, rows >= *n_done are untouched, and the handle is in the state the
+ * last mfea_step left it in (mfea_get_* return the last row).
+ * One partition only: a handle with more (mfea_debug_set_parts, an RCCL
+ * world) returns MFEA_ESTATE. */
+typedef struct {
+  double* U;         /* n_steps × 3·n_nodes, row k = step k, original node order; NULL = not kept */
+  double* stress;    /* n_steps × n_elems; NULL = not kept                                        */
+  uint8_t* active;   /* n_steps × n_elems, activity after the step's failures; NULL = not kept    */
+  double* force;     /* n_steps: total_force of step k (required)                                 */
+  int64_t* n_active; /* n_steps (required)                                                        */
+  mfea_stats* stats; /* n_steps, or NULL                                                          */
+  double* wall_s;    /* n_steps, or NULL: host wall time of step k's mfea_step (what the drivers
+                        write to solve_runtime.txt)                                               */
+} mfea_run_records;
+
+#define MFEA_RUN_COMPLETE 0  /* all n_steps ran                          */
+#define MFEA_RUN_NO_ACTIVE 1 /* n_active reached 0 after step n_done - 1 */
+
+int mfea_run(mfea_handle* h, int32_t n_steps, const double* dy_top, const double* dy_bot,
+             const mfea_solve_opts* opts, double max_strain, const mfea_run_records* rec,
+             int32_t* n_done, int32_t* stop_reason);
+
 /* ---- reference-API helpers ------------------------------------------------- */
 /* bar_stiffness_bulk on device (src/fea_solver.py:30-68): Ke n×36 row-major, L n. */
 int mfea_element_stiffness(mfea_handle* h, int64_t n, const double* p1s, const double* p2s,

@@ -105,6 +105,10 @@ int mfea_debug_floating(mfea_handle* h, uint8_t* out);
  *                        batch that was not the last has its post's failures undone
  *   "asm_kernel" 0|1|2   assembly: row gather, GAMG RHS fused (0); element colours, one
  *                        launch per colour (1); element pass + row pass (2) — DESIGN.md §0
+ *   "run_register" 0|1   mfea_run: page-lock the caller's record arrays for the call and copy
+ *                        each row straight into them (1); 0: through two pinned host slabs
+ *                        and a host memcpy (the path taken when page-locking fails).
+ *                        Read-only "run_direct": which of the two the last mfea_run took
  * Read-only: "sweep_colors", "sweep_pieces" (the last SOR / ICC plan), "asm_colours"
  * (the element colouring's colours once asm_kernel 1 or 2 has run; 0 before).
  * Options that change the symbolic layout rebuild it at the next call. */

@@ -25,6 +25,7 @@
 #include "mfea.h"
 #include "partition.hpp"
 #include "records.hpp"
+#include "run.hpp"
 #include "symbolic.hpp"
 
 using namespace mfea;
@@ -210,6 +211,11 @@ struct Part {
   XDev xd_c, xd_spt, xd_sd;  // the compact cycle split at level 0 (AmgRank::compact)
   DevBuf<int32_t> amg_xi;
   DevBuf<double> amg_xs, amg_xr;
+  // mfea_run (run.hpp): iperm of this build's pattern and the two staging
+  // slabs, allocated at the first run after a (re)build
+  DevBuf<int32_t> iperm_d;
+  DevBuf<uint8_t> rec_slab[2];
+  bool rec_ok = false;
 };
 
 struct mfea_handle {
@@ -407,6 +413,15 @@ struct mfea_handle {
     int choice = -1;
     double t[2] = {-1.0, -1.0};
   } amg_auto;
+  // mfea_run: the copy stream, per staging slab a "rows gathered" event (the
+  // handle's stream) and a "slab free" event (the copy stream), and the two
+  // pinned host slabs of the path without registered record arrays
+  hipStream_t run_copy = nullptr;
+  hipEvent_t run_ready[2] = {}, run_free[2] = {};
+  uint8_t* run_pin[2] = {};
+  size_t run_pin_bytes = 0;
+  bool opt_run_register = true;  // option "run_register": page-lock the caller's record arrays
+  int run_direct = 0;            // read-only option "run_direct": the last run copied straight into them
   // generic CSR path scratch
   DevBuf<int64_t> c_indptr;
   DevBuf<int32_t> c_indices;
@@ -3527,6 +3542,15 @@ int mfea_destroy(mfea_handle* h) {
   if (h->ev_setup) (void)hipEventDestroy(h->ev_setup);
   if (h->h_state) (void)hipHostFree(h->h_state);
   if (h->h_red) (void)hipHostFree(h->h_red);
+  if (h->run_copy) {
+    (void)hipStreamSynchronize(h->run_copy);
+    (void)hipStreamDestroy(h->run_copy);
+  }
+  for (int i = 0; i < 2; ++i) {
+    if (h->run_ready[i]) (void)hipEventDestroy(h->run_ready[i]);
+    if (h->run_free[i]) (void)hipEventDestroy(h->run_free[i]);
+    if (h->run_pin[i]) (void)hipHostFree(h->run_pin[i]);
+  }
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return 0;
@@ -3771,6 +3795,191 @@ int mfea_get_active(mfea_handle* h, uint8_t* active) {
       if (pt.plan.elem_own[le]) active[pt.plan.elem_g[le]] = al[le];
   }
   return 0;
+}
+
+// ---------------------------------------------------------------------------
+// mfea_run: the step loop with the records gathered on the device (run.hpp).
+//
+//   handle stream  step k | gather k → slab k&1 | step k+1 | gather k+1 | ...
+//                              ↓ run_ready[k&1]        ↑ run_free[k&1] (before gather k+2)
+//   copy stream            D2H slab k&1 → row k  ----→
+//
+// The gather reads x / stress / active on the handle's stream, behind the
+// step's post (and the undo of a speculative one), so the rows are what the
+// getters would return; the copy stream only ever reads the slabs.
+// ---------------------------------------------------------------------------
+namespace {
+
+// the caller's record arrays, page-locked for the call
+struct RunRegistered {
+  void* ptr[3] = {};
+  int n = 0;
+  void release() {
+    for (int i = 0; i < n; ++i) (void)hipHostUnregister(ptr[i]);
+    n = 0;
+  }
+  ~RunRegistered() { release(); }
+};
+
+struct RunCtx {
+  RecordSlab L;
+  bool direct = true;
+  uint8_t* dst[3] = {};  // U, stress, active rows of the caller (NULL = not kept)
+  size_t row_b[3] = {};  // bytes per row
+  int64_t off[3] = {};   // offsets in a slab
+  int32_t pending = -1;  // pinned path: the row whose D2H is issued and not yet copied to dst
+};
+
+// the copy stream, events, iperm and the staging slabs of this build
+int run_prepare(mfea_handle* h, Part& pt, const RecordSlab& L) {
+  if (!h->run_copy) HIPC(hipStreamCreateWithFlags(&h->run_copy, hipStreamNonBlocking));
+  for (int i = 0; i < 2; ++i) {
+    if (!h->run_ready[i]) HIPC(hipEventCreateWithFlags(&h->run_ready[i], hipEventDisableTiming));
+    if (!h->run_free[i]) HIPC(hipEventCreateWithFlags(&h->run_free[i], hipEventDisableTiming));
+  }
+  if (pt.rec_ok) return 0;
+  const int64_t N = pt.P.n_nodes;
+  if ((int64_t)pt.P.iperm.size() != N) return fail(MFEA_EINVAL, "internal: iperm does not cover the nodes");
+  for (int64_t g = 0; g < N; ++g)
+    if (pt.P.iperm[g] < 0 || pt.P.iperm[g] >= N) return fail(MFEA_EINVAL, "internal: iperm entry out of range");
+  HIPC(pt.iperm_d.alloc(N));
+  if (N) HIPC(hmemcpy(h, pt.iperm_d.ptr, pt.P.iperm.data(), N * sizeof(int32_t), hipMemcpyHostToDevice));
+  for (auto& sl : pt.rec_slab) HIPC(sl.alloc((size_t)L.bytes));
+  pt.rec_ok = true;
+  return 0;
+}
+
+int run_pinned(mfea_handle* h, size_t bytes) {
+  if (h->run_pin[0] && h->run_pin[1] && h->run_pin_bytes >= bytes) return 0;
+  for (auto& p : h->run_pin) {
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+  }
+  h->run_pin_bytes = 0;
+  for (auto& p : h->run_pin) HIPC(hipHostMalloc((void**)&p, std::max<size_t>(bytes, 1), hipHostMallocDefault));
+  h->run_pin_bytes = bytes;
+  return 0;
+}
+
+// pinned path: row k's copy has been issued; wait for it and move it to the caller's row
+int run_drain(mfea_handle* h, RunCtx& c) {
+  if (c.pending < 0) return 0;
+  const int32_t k = c.pending;
+  c.pending = -1;
+  HIPC(hipEventSynchronize(h->run_free[k & 1]));
+  for (int j = 0; j < 3; ++j)
+    if (c.dst[j] && c.row_b[j])
+      std::memcpy(c.dst[j] + (size_t)k * c.row_b[j], h->run_pin[k & 1] + c.off[j], c.row_b[j]);
+  return 0;
+}
+
+int run_steps(mfea_handle* h, Part& pt, RunCtx& c, int32_t n_steps, const double* dy_top, const double* dy_bot,
+              const mfea_solve_opts* opts, double max_strain, const mfea_run_records* rec, int32_t* n_done,
+              int32_t* stop_reason) {
+  const int64_t N = pt.P.n_nodes, E = pt.P.n_elems;
+  for (int32_t k = 0; k < n_steps; ++k) {
+    double force = 0.0;
+    int64_t na = 0;
+    mfea_stats st;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = mfea_step(h, dy_top[k], dy_bot[k], opts, max_strain, &force, &na, &st);
+    const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (rc == MFEA_EMAXIT || rc == MFEA_EBREAKDOWN) {
+      *stop_reason = rc;
+      return 0;
+    }
+    if (rc) return rc;
+    rec->force[k] = force;
+    rec->n_active[k] = na;
+    if (rec->stats) rec->stats[k] = st;
+    if (rec->wall_s) rec->wall_s[k] = wall;
+    const int s = k & 1;
+    uint8_t* slab = pt.rec_slab[s].ptr;
+    // slab s was last read by the copies of step k - 2
+    if (k >= 2) HIPC(hipStreamWaitEvent(h->stream, h->run_free[s], 0));
+    launch_record_step(h->stream, N, pt.iperm_d.ptr, pt.x.ptr,
+                       c.dst[0] ? reinterpret_cast<double*>(slab + c.off[0]) : nullptr, E, pt.stress.ptr,
+                       c.dst[1] ? reinterpret_cast<double*>(slab + c.off[1]) : nullptr, pt.active.ptr,
+                       c.dst[2] ? slab + c.off[2] : nullptr);
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(h->run_ready[s], h->stream));
+    HIPC(hipStreamWaitEvent(h->run_copy, h->run_ready[s], 0));
+    for (int j = 0; j < 3; ++j) {
+      if (!c.dst[j] || !c.row_b[j]) continue;
+      uint8_t* to = c.direct ? c.dst[j] + (size_t)k * c.row_b[j] : h->run_pin[s] + c.off[j];
+      HIPC(hipMemcpyAsync(to, slab + c.off[j], c.row_b[j], hipMemcpyDeviceToHost, h->run_copy));
+    }
+    HIPC(hipEventRecord(h->run_free[s], h->run_copy));
+    if (!c.direct) {
+      // row k - 1 was copied out while step k ran: move it now, while row k's
+      // copy runs, before step k + 1's copy reuses its pinned slab
+      RC(run_drain(h, c));
+      c.pending = k;
+    }
+    *n_done = k + 1;
+    if (na == 0) {
+      *stop_reason = MFEA_RUN_NO_ACTIVE;
+      return 0;
+    }
+  }
+  return 0;
+}
+
+}  // namespace
+
+int mfea_run(mfea_handle* h, int32_t n_steps, const double* dy_top, const double* dy_bot,
+             const mfea_solve_opts* opts, double max_strain, const mfea_run_records* rec, int32_t* n_done,
+             int32_t* stop_reason) {
+  if (!h || !rec || !n_done || !stop_reason) return fail(MFEA_EINVAL, "NULL argument");
+  if (n_steps < 0) return fail(MFEA_EINVAL, "negative n_steps");
+  if (n_steps && (!dy_top || !dy_bot || !rec->force || !rec->n_active))
+    return fail(MFEA_EINVAL, "mfea_run: dy_top, dy_bot, force and n_active are required");
+  *n_done = 0;
+  *stop_reason = MFEA_RUN_COMPLETE;
+  RC(set_device(h));
+  RC(ensure_built(h));
+  if (partitioned(h))
+    return fail(MFEA_ESTATE, "mfea_run: one partition per handle (the records of a partitioned handle "
+                             "need its ownership maps on the device)");
+  if (n_steps == 0) return 0;
+  Part& pt = part0(h);
+  RunCtx c;
+  c.L = record_slab(pt.P.n_nodes, pt.P.n_elems);
+  RC(run_prepare(h, pt, c.L));
+  c.dst[0] = reinterpret_cast<uint8_t*>(rec->U);
+  c.dst[1] = reinterpret_cast<uint8_t*>(rec->stress);
+  c.dst[2] = rec->active;
+  c.row_b[0] = (size_t)pt.P.n_nodes * 24;
+  c.row_b[1] = (size_t)pt.P.n_elems * 8;
+  c.row_b[2] = (size_t)pt.P.n_elems;
+  c.off[0] = c.L.off_u;
+  c.off[1] = c.L.off_s;
+  c.off[2] = c.L.off_a;
+  RunRegistered reg;
+  c.direct = h->opt_run_register;
+  for (int j = 0; j < 3 && c.direct; ++j) {
+    if (!c.dst[j] || !c.row_b[j]) continue;
+    if (hipHostRegister(c.dst[j], (size_t)n_steps * c.row_b[j], hipHostRegisterDefault) == hipSuccess) {
+      reg.ptr[reg.n++] = c.dst[j];
+    } else {
+      (void)hipGetLastError();
+      c.direct = false;
+    }
+  }
+  if (!c.direct) {
+    reg.release();
+    RC(run_pinned(h, (size_t)c.L.bytes));
+  }
+  h->run_direct = c.direct ? 1 : 0;
+  int rc = run_steps(h, pt, c, n_steps, dy_top, dy_bot, opts, max_strain, rec, n_done, stop_reason);
+  // every exit: the copies issued so far land before the arrays are released
+  const int rd = run_drain(h, c);
+  const hipError_t es = hipStreamSynchronize(h->run_copy);
+  reg.release();
+  if (rc == 0) rc = rd;
+  if (rc == 0 && es != hipSuccess)
+    rc = fail(MFEA_EDEVICE, std::string("mfea_run: copy stream: ") + hipGetErrorString(es));
+  return rc;
 }
 
 int mfea_element_stiffness(mfea_handle* h, int64_t n, const double* p1s, const double* p2s,
@@ -4133,6 +4342,7 @@ int mfea_set_option(mfea_handle* h, const char* name, int64_t value) {
   const std::string n(name);
   bool rebuild = false;  // options baked into the symbolic layout
   if (n == "graph") h->opt_graph = value != 0;
+  else if (n == "run_register") h->opt_run_register = value != 0;
   else if (n == "phase_times") h->opt_phase_times = value != 0;
   else if (n == "dist_graph") h->opt_dist_graph = value != 0;
   else if (n == "order") { h->opt_order = (int)value; rebuild = true; }
@@ -4464,6 +4674,8 @@ int mfea_get_option(mfea_handle* h, const char* name, int64_t* value) {
   for (const char* pn : plan_names)
     if (n == pn && h->parts.empty()) return fail(MFEA_ESTATE, std::string(name) + ": no partition yet");
   if (n == "graph") *value = h->opt_graph;
+  else if (n == "run_register") *value = h->opt_run_register ? 1 : 0;
+  else if (n == "run_direct") *value = h->run_direct;  // read-only: the last mfea_run's host path
   else if (n == "phase_times") *value = h->opt_phase_times ? 1 : 0;
   else if (n == "dist_graph") *value = h->opt_dist_graph;
   else if (n == "order") *value = h->opt_order;

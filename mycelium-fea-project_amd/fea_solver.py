@@ -173,7 +173,7 @@ def _grips(nodes, coords, tol):
 
 
 def fea_solver(results_dir, tol=GRIP_LENGTH, *, rtol=None, max_it=None, precond=None,
-               out_format="python", verbose=True, nparts=1, npy=False):
+               out_format="python", verbose=True, nparts=1, npy=False, device_run=False):
     """The reference step loop (src/fea_solver.py:186-335) with the hot path on device.
 
     Reads <results_dir>/nodes.csv + elements.csv, runs N_STEPS load steps and
@@ -189,9 +189,16 @@ def fea_solver(results_dir, tol=GRIP_LENGTH, *, rtol=None, max_it=None, precond=
     rank 0 alone gathers the records and writes the files — the reference's
     MPI variant has every rank write the same files (src/fea_petsc_parallel.cpp:
     491-574).  nparts > 1 in ONE process runs that partitioned solve with its
-    partitions all on this device (mfea_debug_set_parts)."""
+    partitions all on this device (mfea_debug_set_parts).
+
+    device_run=True (one process, one partition) runs the step loop as ONE
+    library call (Engine.run / mfea_run): every step's records are gathered on
+    the device and copied out while the next step computes.  Same files, same
+    returned dict; the per-step progress lines are printed after the run."""
     start_time = time.time()
     rank, world = dist_env()
+    if device_run and (world > 1 or nparts > 1):
+        raise ValueError("device_run needs one process and one partition (world == 1, nparts == 1)")
     say = print if verbose and rank == 0 else (lambda *a, **k: None)
     say(f"🔧 Running FEA on geometry from {results_dir}")
     fea_dir = os.path.join(results_dir, "fea_results")
@@ -226,7 +233,9 @@ def fea_solver(results_dir, tol=GRIP_LENGTH, *, rtol=None, max_it=None, precond=
     if rank == 0:
         with open(os.path.join(fea_dir, "solve_runtime.txt"), "w") as f:
             f.write("step, runtime_s\n")
-    for step in range(N_STEPS):
+    if device_run:
+        stress_record, active_record, disp_record, force_disp_curve = _device_run(eng, opts, fea_dir, say)
+    for step in range(0 if device_run else N_STEPS):  # the per-step path
         disp_factor = step / (N_STEPS - 1)
         dy_top = +DISPLACEMENT_MAX * disp_factor
         dy_bot = -DISPLACEMENT_MAX * disp_factor
@@ -267,6 +276,30 @@ def fea_solver(results_dir, tol=GRIP_LENGTH, *, rtol=None, max_it=None, precond=
             "active": np.asarray(active_record), "U": np.asarray(disp_record)}
 
 
+def _device_run(eng, opts, fea_dir, say):
+    """The step loop of fea_solver as one library call (Engine.run / mfea_run):
+    the same dy schedule, the same progress lines (printed after the run),
+    solve_runtime.txt from the call's per-step wall times.  Returns the four
+    records as the loop would have collected them."""
+    dys = [(+DISPLACEMENT_MAX * (step / (N_STEPS - 1)), -DISPLACEMENT_MAX * (step / (N_STEPS - 1)))
+           for step in range(N_STEPS)]
+    run = eng.run([d[0] for d in dys], [d[1] for d in dys], opts, MAX_STRAIN)
+    n_done = run["n_done"]
+    with open(os.path.join(fea_dir, "solve_runtime.txt"), "a") as f:
+        for step in range(n_done):
+            say(f"➡️  Step {step+1}/{N_STEPS} | dy_top={dys[step][0]:.3f}, dy_bot={dys[step][1]:.3f}")
+            f.write(f"{step+1}, {run['wall_s'][step]:.6f}\n")
+    if run["stop_reason"] in (_capi.EMAXIT, _capi.EBREAKDOWN):
+        say(f"➡️  Step {n_done+1}/{N_STEPS} | dy_top={dys[n_done][0]:.3f}, dy_bot={dys[n_done][1]:.3f}")
+        say(f"❌ Singular matrix at step {n_done+1}. Saving partial results and stopping.")
+    elif run["stop_reason"] == _capi.RUN_NO_ACTIVE:
+        say(f"⚠️  Simulation stopped early at step {n_done}.")
+    if not n_done:  # empty lists, as the loop leaves them
+        return [], [], [], []
+    force_disp_curve = [[dys[k][0] - dys[k][1], float(run["force"][k])] for k in range(n_done)]
+    return run["stress"], run["active"], run["U"], force_disp_curve
+
+
 def write_records(fea_dir, n_nodes, n_elems, stress_record, active_record, disp_record,
                   force_disp_curve, out_format="python", npy=False):
     """CSV writers, src/fea_solver.py:297-316 (pandas) / src/fea_petsc.cpp:433-516,
@@ -301,6 +334,9 @@ def main(argv=None):
     ap.add_argument("--pc", choices=["gamg", "jacobi", "bjacobi", "sor", "icc"], default="gamg")
     ap.add_argument("--format", choices=["python", "petsc"], default="python")
     ap.add_argument("--npy", action="store_true", help="also write each record as a .npy sidecar")
+    ap.add_argument("--device-run", action="store_true",
+                    help="run the step loop as one library call, the records gathered on the device "
+                         "(one process, one partition)")
     ap.add_argument("--parts", type=int, default=1,
                     help="partitions of the multi-GPU solve, all on this device (one process); "
                          "for one GPU per process launch with torch.distributed.run instead")
@@ -309,7 +345,7 @@ def main(argv=None):
     fea_solver(a.results_dir, tol=a.grip_length, rtol=a.rtol, max_it=a.max_it,
                precond={"gamg": _capi.PC_GAMG, "jacobi": _capi.PC_JACOBI,
                         "bjacobi": _capi.PC_BLOCK_JACOBI, "sor": _capi.PC_SOR, "icc": _capi.PC_ICC}[a.pc],
-               out_format=a.format, nparts=a.parts, npy=a.npy)
+               out_format=a.format, nparts=a.parts, npy=a.npy, device_run=a.device_run)
 
 
 if __name__ == "__main__":

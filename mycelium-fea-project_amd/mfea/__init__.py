@@ -6,4 +6,5 @@ reference's ``src/fea_solver.py`` API is ``fea_solver`` next to this package.
 from ._capi import (Engine, MfeaError, SolverFailure, SolveOpts, Stats, abi_version,  # noqa: F401
                     make_opts, PC_JACOBI, PC_BLOCK_JACOBI, PC_GAMG, PC_SOR, PC_ICC, NORM_PRECONDITIONED,
                     NORM_UNPRECONDITIONED, LIB_PATH, dist_unique_id,
-                    GrowParams, grow_params, scaled_grow_params, grow_network)
+                    GrowParams, grow_params, scaled_grow_params, grow_network,
+                    RunRecords, RUN_COMPLETE, RUN_NO_ACTIVE)

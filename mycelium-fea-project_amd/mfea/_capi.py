@@ -23,7 +23,7 @@ DEFAULT_OPTIONS = {"graph": 1, "phase_times": 0, "dist_graph": 1, "order": -1, "
                    "amg_coarse_rho_ppm": 1750000, "sweep_piece": 64, "cc_tile": 1024,
                    "asm_kernel": 0, "spec_post": 1, "setup_entry": 1,
                    "batch_graph": 1, "step_graph": 0,
-                   "graph_start": 1, "combo_graph": 1, "amg_a0_slot": 1}
+                   "graph_start": 1, "combo_graph": 1, "amg_a0_slot": 1, "run_register": 1}
 CG_KERNEL = {"auto": 0, "lanes": 1, "sell": 2}
 
 LIB_PATH = os.environ.get("MFEA_LIB", os.path.join(os.path.dirname(_HERE), "libmfea.so"))
@@ -39,6 +39,7 @@ OK, EINVAL, EDEVICE, ESTATE, EMAXIT, EBREAKDOWN, ENOMEM, ECOMM = 0, -1, -2, -3, 
 PC_JACOBI, PC_BLOCK_JACOBI, PC_GAMG, PC_SOR, PC_ICC = 0, 1, 2, 3, 4
 NORM_UNPRECONDITIONED, NORM_PRECONDITIONED = 0, 1
 MESH_SKIP_INVALID = 1
+RUN_COMPLETE, RUN_NO_ACTIVE = 0, 1  # mfea_run's stop_reason (or EMAXIT / EBREAKDOWN)
 
 
 class SolveOpts(C.Structure):
@@ -55,6 +56,13 @@ class Stats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class RunRecords(C.Structure):
+    """mfea_run_records (include/mfea.h): where mfea_run writes each step's rows."""
+    _fields_ = [("U", C.c_void_p), ("stress", C.c_void_p), ("active", C.c_void_p),
+                ("force", C.c_void_p), ("n_active", C.c_void_p), ("stats", C.POINTER(Stats)),
+                ("wall_s", C.c_void_p)]
 
 
 class Info(C.Structure):
@@ -102,6 +110,8 @@ _sig = {
     "mfea_post": (C.c_int, [_P, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "mfea_step": (C.c_int, [_P, C.c_double, C.c_double, C.POINTER(SolveOpts), C.c_double,
                             C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(Stats)]),
+    "mfea_run": (C.c_int, [_P, C.c_int32, _P, _P, C.POINTER(SolveOpts), C.c_double,
+                           C.POINTER(RunRecords), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mfea_get_displacement": (C.c_int, [_P, _P]),
     "mfea_get_stress": (C.c_int, [_P, _P]),
     "mfea_get_active": (C.c_int, [_P, _P]),
@@ -411,6 +421,58 @@ class Engine:
         _check(_lib.mfea_step(self._h, float(dy_top), float(dy_bot), C.byref(o), float(max_strain),
                               C.byref(f), C.byref(n), C.byref(st)), st)
         return f.value, n.value, st
+
+    def run(self, dy_top, dy_bot, opts: SolveOpts | None, max_strain, keep=("U", "stress", "active"),
+            out=None):
+        """The whole step loop in one call (mfea_run): step k is
+        step(dy_top[k], dy_bot[k], opts, max_strain), its records gathered on
+        the device and copied out while step k + 1 computes.  keep: which of
+        "U", "stress", "active" to record (the others are None).  out: optional
+        dict of preallocated C-contiguous n_steps × cols arrays to write into
+        (U / stress float64, active uint8); rows >= n_done stay as they were.
+        Returns a dict: the records cut to [:n_done] (active as bool), force,
+        n_active, stats (list of dicts), wall_s, n_done and stop_reason
+        (RUN_COMPLETE, RUN_NO_ACTIVE, EMAXIT or EBREAKDOWN — a solver stop does
+        not raise)."""
+        dyt = np.ascontiguousarray(dy_top, dtype=np.float64).ravel()
+        dyb = np.ascontiguousarray(dy_bot, dtype=np.float64).ravel()
+        if dyt.size != dyb.size:
+            raise ValueError("dy_top and dy_bot must have one entry per step")
+        n = dyt.size
+        unknown = set(keep) - {"U", "stress", "active"}
+        if unknown:
+            raise ValueError(f"unknown record(s) {sorted(unknown)}")
+        spec = {"U": (3 * self.n_nodes, np.float64), "stress": (self.n_elems, np.float64),
+                "active": (self.n_elems, np.uint8)}
+        arr = {}
+        for name, (cols, dt) in spec.items():
+            if name not in keep:
+                arr[name] = None
+                continue
+            a = (out or {}).get(name)
+            if a is None:
+                a = np.empty((n, cols), dtype=dt)
+            elif a.dtype != dt or a.shape != (n, cols) or not a.flags.c_contiguous:
+                raise ValueError(f"out[{name!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {(n, cols)}")
+            arr[name] = a
+        force = np.zeros(n)
+        n_active = np.zeros(n, dtype=np.int64)
+        wall = np.zeros(n)
+        stats = (Stats * max(n, 1))()
+        rec = RunRecords(*(arr[k].ctypes.data if arr[k] is not None and arr[k].size else None
+                           for k in ("U", "stress", "active")),
+                         force.ctypes.data, n_active.ctypes.data, stats, wall.ctypes.data)
+        o = opts if opts is not None else make_opts()
+        n_done, stop = C.c_int32(), C.c_int32()
+        _check(_lib.mfea_run(self._h, n, _ptr(dyt), _ptr(dyb), C.byref(o), float(max_strain), C.byref(rec),
+                             C.byref(n_done), C.byref(stop)))
+        m = n_done.value
+        res = {k: (None if a is None else a[:m]) for k, a in arr.items()}
+        if res["active"] is not None:
+            res["active"] = res["active"].astype(bool)
+        res.update(force=force[:m], n_active=n_active[:m], stats=[stats[i].as_dict() for i in range(m)],
+                   wall_s=wall[:m], n_done=m, stop_reason=stop.value)
+        return res
 
     # ---- results --------------------------------------------------------------
     def displacement(self):
