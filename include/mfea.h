@@ -150,7 +150,24 @@ int mfea_solve(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_op
  * unregularised K; stress = E·ε for elements active at step start (0 else);
  * elements with |ε| > max_strain are deactivated for the next step. */
 int mfea_post(mfea_handle* h, double max_strain, double* total_force, int64_t* n_active);
-/* One full load step = assemble + solve + post (the bench "step"). */
+/* One full load step = assemble + solve + post (the bench "step").
+ * On a handle with one partition the step keeps what the grip displacements
+ * do not enter (option "keep_operator", on by default; mfea_debug.h):
+ *   - K, while the element activity (mfea_set_active with a mask, failures
+ *     reported by a post), the material, the build (mfea_set_mesh / mfea_set_bc,
+ *     a layout option) and the assembly kernel are those of the last assembly:
+ *     the step then forms only its right-hand side, with the kernel mfea_solve
+ *     uses after mfea_assemble;
+ *   - the GAMG hierarchy's values, while K, the hierarchy's plan, its floating-
+ *     row mask, opts->reg and the smoothing weights are those of the last
+ *     numeric setup, and the solve behind that setup converged.
+ * rtol, atol and max_it are no inputs of either.  A step that returns an error,
+ * any mfea_set_option but "phase_times" / "run_register", a solve with another
+ * preconditioner kind (the hierarchy's values only) and the profiling / debug
+ * entry points of mfea_debug.h drop what is kept; mfea_assemble always assembles.
+ * Results are bit for bit those of a step that assembles and sets up.
+ * With "phase_times" a kept step reports the RHS launch as t_assemble_ms and
+ * t_setup_ms = 0. */
 int mfea_step(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opts* opts,
               double max_strain, double* total_force, int64_t* n_active, mfea_stats* st);
 

@@ -109,6 +109,14 @@ int mfea_debug_floating(mfea_handle* h, uint8_t* out);
  *                        each row straight into them (1); 0: through two pinned host slabs
  *                        and a host memcpy (the path taken when page-locking fails).
  *                        Read-only "run_direct": which of the two the last mfea_run took
+ *   "keep_operator" 0|1  mfea_step, one partition: keep K while the active set, the material,
+ *                        the build and asm_kernel hold (only the RHS is formed), and keep the
+ *                        GAMG hierarchy's values while K, the plan, the floating mask, reg
+ *                        and ω hold (1; 0: assemble and set up every step).  Every other
+ *                        option set drops both, but phase_times and run_register.
+ *                        Read-only totals since mfea_create: "op_kept_steps" (steps that
+ *                        skipped the assembly), "amg_setup_kept" (solves that skipped the
+ *                        numeric setup) — mfea.h mfea_step, DESIGN.md §4.7
  * Read-only: "sweep_colors", "sweep_pieces" (the last SOR / ICC plan), "asm_colours"
  * (the element colouring's colours once asm_kernel 1 or 2 has run; 0 before).
  * Options that change the symbolic layout rebuild it at the next call. */

@@ -142,6 +142,16 @@ struct Part {
   bool amg_ok = false;
   std::vector<uint8_t> amg_key;
   int64_t amg_gen = 0;               // bumped on every rebuild (captured graphs hold its pointers)
+  int64_t fmask_gen = 0;             // bumped on every enqueue_fmask (the setup reads amg_fmask)
+  // what the hierarchy's values were last formed from (option keep_operator):
+  // the setup launches' arguments (key), K, the plan, the floating mask; ok
+  // only once the solve behind that setup ended with status 0.  ω: every
+  // change goes through apply_coarse_omega, which clears ok.
+  struct {
+    bool ok = false;
+    uint64_t key = 0;
+    int64_t op_gen = -1, amg_gen = -1, fmask_gen = -1;
+  } kept;
   int amg_last_iters = 0;            // iterations of the last converged GAMG solve (chunk plan)
   // a hierarchy kept over element failures (option amg_reuse): the activity
   // its floating-row mask reflects, the iterations of its first solve, and
@@ -260,14 +270,18 @@ struct mfea_handle {
   hipGraphExec_t graph_batch[kRemGraphs] = {};
   // ... and (option "combo_graph") behind the numeric setup in the setup's
   // graph: one graph launch per step, one cached graph per batch length
-  hipGraphExec_t graph_combo[kRemGraphs] = {};
-  uint64_t graph_combo_key[kRemGraphs] = {};
+  // Both in two forms, cached side by side — [0] with the numeric setup, [1]
+  // without it (option keep_operator: a kept setup, or one launched as its
+  // own graph in front, solve_amg) — so a run that goes from kept steps to a
+  // failure step and back replays, never recaptures
+  hipGraphExec_t graph_combo[2][kRemGraphs] = {};
+  uint64_t graph_combo_key[2][kRemGraphs] = {};
   int graph_batch_ell = -1;
   double graph_batch_strain = 0.0;
   // GAMG: the numeric setup's launches (≈ 30) as one graph, keyed by a hash
   // of every argument they take (the level views, the level-0 operator, reg)
-  hipGraphExec_t graph_setup = nullptr;
-  uint64_t graph_setup_key = 0;
+  hipGraphExec_t graph_setup[2] = {};  // ([1]: the head / entry launches alone)
+  uint64_t graph_setup_key[2] = {};
   hipEvent_t ev[6] = {};
   hipEvent_t ev_setup = nullptr;
   // option "phase_times": record the phase events (mfea_stats t_*_ms).  Off by
@@ -302,6 +316,25 @@ struct mfea_handle {
   int opt_graph_start = 1;  // the CG start (k_cg_init_finalize) at the setup graph's head
   // with batch_graph: the batch, finish and post behind the setup in one graph
   int opt_combo_graph = 1;
+  // One partition (option "keep_operator"): mfea_step keeps K
+  // (val / diag) while what it was assembled from holds — the activity
+  // (act_gen), the material, the build (`assembled`), the assembly kernel —
+  // and solve_amg keeps the numeric setup's values while K (op_gen) and the
+  // setup's other inputs hold (Part::kept).  None of them depends on the grip
+  // displacements, the only thing that moves from one load step to the next.
+  int opt_keep_operator = 1;
+  int64_t op_gen = 0;  // bumped by every launch that writes val / diag
+  struct {
+    bool ok = false;
+    int64_t act_gen = -1;
+    Material mat{};
+    int asm_kernel = -1;
+  } k_from;
+  int last_precond = -1;          // the last solve's preconditioner kind
+  int64_t op_kept_steps = 0;      // read-only option: steps that skipped the assembly
+  int64_t amg_setup_kept = 0;     // read-only option: solves that skipped the numeric setup
+  bool setup_skipped = false;     // the last solve did (phase times: t_setup_ms = 0)
+  Material graph_batch_mat{};     // the material graph_batch's post kernels were captured with
   bool asm_pending = false;  // mfea_step deferred its assembly to solve_amg
   DevBuf<double> d_dy;
   bool spec_on = false;
@@ -444,6 +477,29 @@ constexpr int64_t kRecMax = 9, kMMax = 6;  // record / M widths at nd = 3, block
 Part& part0(mfea_handle* h) { return *h->parts[0]; }
 bool partitioned(const mfea_handle* h) { return h->parts.size() > 1 || h->world > 1; }
 int nranks(const mfea_handle* h) { return h->world > 1 ? h->world : (int)h->parts.size(); }
+
+// option keep_operator: forget what K and the hierarchies' values were formed
+// from — the next step assembles, the next GAMG solve sets up
+void drop_kept_setup(mfea_handle* h) {
+  for (auto& pp : h->parts) pp->kept.ok = false;
+}
+void drop_kept(mfea_handle* h) {
+  h->k_from.ok = false;
+  drop_kept_setup(h);
+}
+// K (val / diag) is what an assembly would write now
+bool k_current(const mfea_handle* h) {
+  return h->opt_keep_operator && h->assembled && h->k_from.ok && h->k_from.act_gen == h->act_gen &&
+         std::memcmp(&h->k_from.mat, &h->mat, sizeof h->mat) == 0 && h->k_from.asm_kernel == h->opt_asm_kernel;
+}
+// ... recorded by every launch that writes them
+void k_written(mfea_handle* h) {
+  ++h->op_gen;
+  h->k_from.ok = true;
+  h->k_from.act_gen = h->act_gen;
+  h->k_from.mat = h->mat;
+  h->k_from.asm_kernel = h->opt_asm_kernel;
+}
 
 // ticket set k (one per reducing kernel kind; see device_util.hpp layout)
 unsigned* tix(Part& pt, int k) { return pt.tickets.ptr + (size_t)k * kTicketStride; }
@@ -748,6 +804,9 @@ int ensure_built(mfea_handle* h) {
     }
     h->act_count = (int64_t)std::count(h->act_host.begin(), h->act_host.end(), (uint8_t)1);
     h->act_host_ok = true;
+    // (the count the first post will report: it only moves act_gen, and with
+    // it the kept K, when elements did fail)
+    h->n_active = h->act_count;
   }
   h->active_host.clear();
   h->dirty = false;
@@ -1172,7 +1231,7 @@ void solve_times(mfea_handle* h, mfea_stats* st) {
   st->t_solve_ms = ms;
   if (h->ev_setup_used) {
     (void)hipEventElapsedTime(&ms, h->ev[2], h->ev_setup);
-    st->t_setup_ms = ms;
+    st->t_setup_ms = h->setup_skipped ? 0.0 : ms;  // (kept values: the event is recorded, nothing ran before it)
   }
 }
 
@@ -1345,6 +1404,7 @@ int apply_coarse_omega(mfea_handle* h, Part& pt) {
   const int nlev = (int)pt.amg_lev.size();
   const double rho = coarse_rho(h);
   static const double kRho0 = 2.0;
+  pt.kept.ok = false;  // (the kept values hold the old weights' products)
   for (int l = 0; l < nlev; ++l) {
     AmgLevD& d = pt.amg_lev[l];
     d.fixed_omega = pt.amg_om_own && l > 0 && rho > 0.0 ? 1 : 0;
@@ -1725,6 +1785,7 @@ int upload_amg_halo(mfea_handle* h, Part& pt, const std::vector<uint8_t>& key) {
 int enqueue_fmask(mfea_handle* h, Part& pt) {
   const Pattern& P = pt.P;
   if (P.n_free == 0 || !pt.amg_row0_inv) return 0;
+  ++pt.fmask_gen;
   HIPC(pt.cc_parent.alloc(std::max<int64_t>(P.n_nodes, 1)));
   HIPC(pt.cc_anch.alloc(std::max<int64_t>(P.n_nodes, 1)));
   launch_floating(h->stream, P.n_nodes, P.n_free, P.n_nodes - P.n_ghost, pt.slice_ptr.ptr, pt.row_len.ptr,
@@ -2131,10 +2192,9 @@ void enqueue_step_head(mfea_handle* h, Part& pt, const mfea_solve_opts* o) {
 // anything the launches read changes (the key hashes all of it).  entry: the
 // solve's entry launches captured behind the setup (no phase event between
 // them); head (non-null): mfea_step's assembly and CG start before it
-int launch_amg_setup_graph(mfea_handle* h, Part& pt, double reg, bool entry = false,
-                           const mfea_solve_opts* head = nullptr, const mfea_solve_opts* start = nullptr,
-                           int tail = 0, int tag = 0) {
-  hipStream_t s = h->stream;
+// everything enqueue_amg_setup's launches take but K's values and the
+// floating mask's: the level views, the level-0 operator, the options, reg
+uint64_t amg_setup_key(mfea_handle* h, Part& pt, double reg) {
   uint64_t k = 1469598103934665603ULL;
   k = fnv1a(k, pt.amg_lev.data(), pt.amg_lev.size() * sizeof(AmgLevD));
   k = fnv1a(k, &pt.amg_mg, sizeof pt.amg_mg);
@@ -2146,6 +2206,20 @@ int launch_amg_setup_graph(mfea_handle* h, Part& pt, double reg, bool entry = fa
   k = fnv1a(k, &pt.swd, sizeof pt.swd);
   k = fnv1a(k, ints, sizeof ints);
   k = fnv1a(k, &reg, sizeof reg);
+  return k;
+}
+
+// k0: amg_setup_key of these arguments.  keep: the hierarchy's values are
+// current (solve_amg) — the graph without the setup's launches, cached beside
+// the one with them; nothing at all where no head / entry / tail rides along
+int launch_amg_setup_graph(mfea_handle* h, Part& pt, double reg, uint64_t k0, bool keep, bool entry = false,
+                           const mfea_solve_opts* head = nullptr, const mfea_solve_opts* start = nullptr,
+                           int tail = 0, int tag = 0) {
+  hipStream_t s = h->stream;
+  uint64_t k = k0;
+  const int form = keep ? 1 : 0;
+  k = fnv1a(k, &form, sizeof form);
+  if (keep && !entry && !head && !start && tail <= 0) return 0;
   if (entry) {
     const CgVecs v = cg_vecs(pt);
     const void* eptrs[4] = {v.r[0], pt.slots.ptr, pt.state.ptr, pt.cg_part.ptr};
@@ -2178,8 +2252,9 @@ int launch_amg_setup_graph(mfea_handle* h, Part& pt, double reg, bool entry = fa
     k = fnv1a(k ^ 0xc0b0, &tail, sizeof tail);
     k = fnv1a(k, &tag, sizeof tag);
     k = fnv1a(k, &h->spec_strain, sizeof h->spec_strain);
-    hipGraphExec_t& gc = h->graph_combo[tail];
-    if (!gc || h->graph_combo_key[tail] != k) {
+    k = fnv1a(k, &h->mat, sizeof h->mat);  // (the post's stress kernel holds it by value)
+    hipGraphExec_t& gc = h->graph_combo[form][tail];
+    if (!gc || h->graph_combo_key[form][tail] != k) {
       if (gc) {
         HIPC(hipStreamSynchronize(s));
         (void)hipGraphExecDestroy(gc);
@@ -2191,7 +2266,7 @@ int launch_amg_setup_graph(mfea_handle* h, Part& pt, double reg, bool entry = fa
       if (start)
         launch_cg_init_finalize(s, pt.red.ptr, start->rtol, start->atol, start->norm, start->max_it, start->reg,
                                 pt.state.ptr, pt.cg_part.ptr, 2 * 4 * kCgMaxPartials);
-      enqueue_amg_setup(h, pt, reg);
+      if (!keep) enqueue_amg_setup(h, pt, reg);
       enqueue_amg_entry(h, pt);
       enqueue_amg_chunk(h, pt, tail);
       launch_amg_finish(s, pt.amg.nd, pt.amg_cg, pt.x.ptr);
@@ -2202,16 +2277,17 @@ int launch_amg_setup_graph(mfea_handle* h, Part& pt, double reg, bool entry = fa
       const hipError_t e = hipGraphInstantiate(&gc, g, nullptr, nullptr, 0);
       (void)hipGraphDestroy(g);
       HIPC(e);
-      h->graph_combo_key[tail] = k;
+      h->graph_combo_key[form][tail] = k;
     }
     HIPC(hipGraphLaunch(gc, s));
     return 0;
   }
-  if (!h->graph_setup || h->graph_setup_key != k) {
-    if (h->graph_setup) {
+  hipGraphExec_t& gs = h->graph_setup[form];
+  if (!gs || h->graph_setup_key[form] != k) {
+    if (gs) {
       HIPC(hipStreamSynchronize(s));  // no replay of the old graph in flight
-      (void)hipGraphExecDestroy(h->graph_setup);
-      h->graph_setup = nullptr;
+      (void)hipGraphExecDestroy(gs);
+      gs = nullptr;
     }
     hipGraph_t g;
     HIPC(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
@@ -2219,15 +2295,15 @@ int launch_amg_setup_graph(mfea_handle* h, Part& pt, double reg, bool entry = fa
     if (start)
       launch_cg_init_finalize(s, pt.red.ptr, start->rtol, start->atol, start->norm, start->max_it, start->reg,
                               pt.state.ptr, pt.cg_part.ptr, 2 * 4 * kCgMaxPartials);
-    enqueue_amg_setup(h, pt, reg);
+    if (!keep) enqueue_amg_setup(h, pt, reg);
     if (entry) enqueue_amg_entry(h, pt);
     HIPC(hipStreamEndCapture(s, &g));
-    const hipError_t e = hipGraphInstantiate(&h->graph_setup, g, nullptr, nullptr, 0);
+    const hipError_t e = hipGraphInstantiate(&gs, g, nullptr, nullptr, 0);
     (void)hipGraphDestroy(g);
     HIPC(e);
-    h->graph_setup_key = k;
+    h->graph_setup_key[form] = k;
   }
-  HIPC(hipGraphLaunch(h->graph_setup, s));
+  HIPC(hipGraphLaunch(gs, s));
   return 0;
 }
 
@@ -2252,9 +2328,26 @@ int solve_amg(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opt
   const bool head = h->asm_pending && h->opt_graph && !h->opt_phase_times;
   if (h->asm_pending) {
     h->asm_pending = false;
-    if (head) HIPC(h->d_dy.alloc(2));
-    else RC(assemble_impl(h, nullptr, h->h_red + 14));
+    if (head) {
+      HIPC(h->d_dy.alloc(2));
+      k_written(h);  // (the head's k_assemble)
+    } else {
+      RC(assemble_impl(h, nullptr, h->h_red + 14));
+    }
   }
+  // the hierarchy's values are those this setup would form: skip it (the
+  // iteration, entry and finish launches write vectors only — amg.hip)
+  const uint64_t skey = amg_setup_key(h, pt, o->reg);
+  const bool keep = h->opt_keep_operator && !pt.amg_cg.sweep && pt.kept.ok && pt.kept.key == skey &&
+                    pt.kept.op_gen == h->op_gen && pt.kept.amg_gen == pt.amg_gen &&
+                    pt.kept.fmask_gen == pt.fmask_gen;
+  pt.kept.ok = false;  // (set again when this solve ends with status 0)
+  pt.kept.key = skey;
+  pt.kept.op_gen = h->op_gen;
+  pt.kept.amg_gen = pt.amg_gen;
+  pt.kept.fmask_gen = pt.fmask_gen;
+  h->setup_skipped = keep;
+  if (keep) ++h->amg_setup_kept;
   RC(phase_event(h, h->ev[1], s));
   // the CG start inside the setup graph when no phase event separates them
   const bool start_in_graph = h->opt_graph && h->opt_graph_start && !h->opt_phase_times && !head;
@@ -2286,10 +2379,20 @@ int solve_amg(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opt
   // (combo: the graph reaches the batch's end and publishes the state; the
   // host's copy of the flag is cleared before it can)
   if (combo) h->h_state[0].done = 0;
-  if (h->opt_graph)
-    RC(launch_amg_setup_graph(h, pt, o->reg, entry, head ? o : nullptr, start_in_graph ? o : nullptr,
-                              combo ? need : 0, tag));
-  else enqueue_amg_setup(h, pt, o->reg);
+  if (h->opt_graph) {
+    // keep_operator on, a combined step that does set up (a new active set
+    // in a run of kept steps): the setup as its own graph — one capture per
+    // plan — in front of the combined graph WITHOUT it, which the kept steps
+    // of this batch length replay anyway.  One combined graph with the setup
+    // per length would be captured on exactly these steps (≈ 0.4 ms each,
+    // more than the setup it holds); the extra graph launch costs a few µs.
+    const bool split = combo && !keep && h->opt_keep_operator && !head;
+    if (split) RC(launch_amg_setup_graph(h, pt, o->reg, skey, false));
+    RC(launch_amg_setup_graph(h, pt, o->reg, skey, keep || split, entry, head ? o : nullptr,
+                              start_in_graph ? o : nullptr, combo ? need : 0, tag));
+  } else if (!keep) {
+    enqueue_amg_setup(h, pt, o->reg);
+  }
   clk.lap("to the setup graph");
   if (!entry) {
     RC(phase_event(h, h->ev_setup, s));
@@ -2361,13 +2464,15 @@ int solve_amg(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opt
     }
     // (batch_graph: C2 / C3 two graph launches and four eager ones fewer per step)
     if (batch) {
-      if (h->graph_batch_ell != tag || h->graph_batch_strain != h->spec_strain) {
+      if (h->graph_batch_ell != tag || h->graph_batch_strain != h->spec_strain ||
+          std::memcmp(&h->graph_batch_mat, &h->mat, sizeof h->mat) != 0) {
         for (auto& g : h->graph_batch) {
           if (g) (void)hipGraphExecDestroy(g);
           g = nullptr;
         }
         h->graph_batch_ell = tag;
         h->graph_batch_strain = h->spec_strain;
+        h->graph_batch_mat = h->mat;  // (the post's stress kernel holds it by value)
       }
       if (!combo && h->graph_batch[need] == nullptr) {
         hipGraph_t g;
@@ -2433,6 +2538,8 @@ int solve_amg(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opt
       pt.amg_stale = true;  // degraded: the next solve rebuilds for its active set
   }
   rc = finish_solve(h, fin, st);
+  // (no retry or rebuild above re-formed them since: those paths returned)
+  if (rc == 0 && fin.status == 0) pt.kept.ok = true;
   if (st) {
     st->amg_levels = (int32_t)pt.amg_lev.size();
     st->amg_rebuilt = rebuilt ? 1 : 0;
@@ -3173,6 +3280,7 @@ int assemble_impl(mfea_handle* h, mfea_stats* st, const double* rhs_dy = nullptr
   hipStream_t s = h->stream;
   h->assembled = true;
   h->rhs_fused = false;
+  k_written(h);
   RC(phase_event(h, h->ev[0], s));
   for (auto& pp : h->parts) {
     Part& pt = *pp;
@@ -3454,6 +3562,10 @@ int solve_amg_part(mfea_handle* h, double dy_top, double dy_bot, const mfea_solv
 int solve_any(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opts* o,
               mfea_stats* st) {
   h->ev_setup_used = false;
+  h->setup_skipped = false;
+  // another preconditioner kind than the last solve's: its setup runs
+  if (o->precond != h->last_precond) drop_kept_setup(h);
+  h->last_precond = o->precond;
   if (o->precond == MFEA_PC_GAMG) {
     if (!partitioned(h)) return solve_amg(h, dy_top, dy_bot, o, st);
     return solve_amg_part(h, dy_top, dy_bot, o, st);
@@ -3530,9 +3642,11 @@ int mfea_destroy(mfea_handle* h) {
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   destroy_graph(h);
-  if (h->graph_setup) (void)hipGraphExecDestroy(h->graph_setup);
-  for (auto& g : h->graph_combo)
+  for (auto& g : h->graph_setup)
     if (g) (void)hipGraphExecDestroy(g);
+  for (auto& form : h->graph_combo)
+    for (auto& g : form)
+      if (g) (void)hipGraphExecDestroy(g);
   h->parts.clear();
   if (h->comm) (void)ncclCommDestroy(h->comm);
   for (auto& ev : h->ev)
@@ -3564,6 +3678,11 @@ int mfea_set_material(mfea_handle* h, double E, double A, double I) {
   h->mat.EA = E * A;             // src/fea_solver.py:45  (E * A) / L_safe
   h->mat.EI12 = (12.0 * E) * I;  // src/fea_solver.py:58  12 * E * I / L³
   h->mat.E = E;
+  // K and everything formed from it are the old material's: the next step
+  // assembles (k_current compares the material by value) and sets up; the
+  // graphs that hold the material by value are keyed by it (graph_batch_mat,
+  // the combined graph's key)
+  ++h->op_gen;
   return 0;
 }
 
@@ -3649,6 +3768,7 @@ int mfea_set_active(mfea_handle* h, const uint8_t* active) {
   if (!partitioned(h)) {
     h->act_count = (int64_t)std::count(h->act_host.begin(), h->act_host.end(), (uint8_t)1);
     h->act_host_ok = true;
+    h->n_active = h->act_count;  // (as ensure_built)
   }
   return 0;
 }
@@ -3696,7 +3816,26 @@ int mfea_step(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opt
   // one partition, GAMG / SOR / ICC, graphs on, no phase events, the row
   // gather: the assembly rides at the head of the solve's setup graph
   const bool defer = fuse_rhs && h->opt_step_graph && h->opt_graph && !h->opt_phase_times && h->opt_asm_kernel == 0;
-  if (defer) {
+  if (!partitioned(h) && k_current(h)) {
+    // K is what this assembly would write (option keep_operator): only the
+    // RHS depends on the grip displacements — the RHS-only kernel of
+    // mfea_solve, between the assembly's phase events (the Jacobi kinds form
+    // theirs in the solve)
+    hipStream_t s = h->stream;
+    ++h->op_kept_steps;
+    h->rhs_fused = false;
+    RC(phase_event(h, h->ev[0], s));
+    if (fuse_rhs) {
+      Part& pt = part0(h);
+      launch_cg_rhs(s, sell_op(pt), pt.code.ptr, dy_top, dy_bot, o.reg, 2, cg_vecs(pt), pt.partials.ptr, tix(pt, 0),
+                    pt.red.ptr);
+      HIPC(hipGetLastError());
+      h->rhs_fused = true;
+      h->rhs_dy[0] = dy_top;
+      h->rhs_dy[1] = dy_bot;
+    }
+    RC(phase_event(h, h->ev[1], s));
+  } else if (defer) {
     h->h_red[14] = dy_top;
     h->h_red[15] = dy_bot;
     h->asm_pending = true;
@@ -3724,6 +3863,7 @@ int mfea_step(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opt
   if (rc == 0) rc = post_impl(h, max_strain, total_force, n_active, st);
   h->in_step = false;
   if (rc) {
+    drop_kept(h);  // (a failed step: the next one assembles and sets up)
     (void)sync_stream(h);
     return rc;
   }
@@ -4192,6 +4332,7 @@ int mfea_profile_spmv(mfea_handle* h, int reps, double* avg_ms) {
   // partitioned: partition 0's w kernel over its own rows (the plan its device
   // arrays hold: its block-Jacobi hierarchy or its share of the global one)
   Part& pt = part0(h);
+  drop_kept(h);  // (conservative: the profile launches run on the solve's arrays)
   if (!(partitioned(h) ? pt.dev_plan >= 0 : pt.amg_ok)) return fail(MFEA_ESTATE, "profile the SpMV after a GAMG solve");
   hipStream_t s = h->stream;
   const int nd = pt.dev_plan == 1 ? h->gamg.nd : pt.amg.nd;
@@ -4222,6 +4363,7 @@ int mfea_profile_iteration(mfea_handle* h, int precond, int reps, double* avg_ms
   RC(ensure_built(h));
   Part& pt = part0(h);
   hipStream_t s = h->stream;
+  drop_kept(h);  // (conservative: the profile launches run on the solve's arrays)
   if (precond == MFEA_PC_GAMG || precond == MFEA_PC_SOR || precond == MFEA_PC_ICC) {
     if (!pt.amg_ok || pt.amg_kind != precond)
       return fail(MFEA_ESTATE, "profile GAMG / SOR / ICC after a solve with that preconditioner");
@@ -4539,7 +4681,14 @@ int mfea_set_option(mfea_handle* h, const char* name, int64_t value) {
     h->opt_part_slack = value / 100.0;
     rebuild = true;
   }
+  else if (n == "keep_operator") {
+    if (value != 0 && value != 1) return fail(MFEA_EINVAL, "keep_operator: 0 or 1");
+    h->opt_keep_operator = (int)value;
+  }
   else return fail(MFEA_EINVAL, "unknown option " + n);
+  // kept K / hierarchy values: dropped by every option but the few that
+  // cannot change a value (conservative: most options only change launches)
+  if (n != "phase_times" && n != "run_register" && !(n == "keep_operator" && value == 1)) drop_kept(h);
   destroy_graph(h);  // captured graphs hold the old geometry
   if (rebuild) {
     if (!h->dirty && h->Ecount) {  // keep the current activity across the rebuild
@@ -4558,6 +4707,7 @@ int mfea_debug_amg_vcycle(mfea_handle* h, const double* r, double* u) {
   hipStream_t s = h->stream;
   const bool dm = partitioned(h);
   if (dm && !h->opt_amg_dist) return fail(MFEA_ESTATE, "mfea_debug_amg_vcycle: amg_dist 0 is not one operator");
+  drop_kept(h);  // (the setup below re-forms the hierarchy's values at its own reg)
   bool rebuilt = false;
   if (dm) {
     RC(ensure_gamg(h, &rebuilt));
@@ -4745,6 +4895,9 @@ int mfea_get_option(mfea_handle* h, const char* name, int64_t* value) {
   else if (n == "step_graph") *value = h->opt_step_graph;
   else if (n == "graph_start") *value = h->opt_graph_start;
   else if (n == "combo_graph") *value = h->opt_combo_graph;
+  else if (n == "keep_operator") *value = h->opt_keep_operator;
+  else if (n == "op_kept_steps") *value = h->op_kept_steps;    // read-only: steps that skipped the assembly
+  else if (n == "amg_setup_kept") *value = h->amg_setup_kept;  // read-only: solves that skipped the numeric setup
   else if (n == "asm_colours") {
     *value = 0;
     for (auto& pp : h->parts) *value = std::max<int64_t>(*value, pp->ec_state > 0 ? pp->ec.colors : 0);

@@ -20,7 +20,8 @@ def main():
         for r in csv.DictReader(f):
             rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), short(r["Kernel_Name"])))
     rows.sort()
-    starts = [i for i, r in enumerate(rows) if r[2].startswith("k_assemble")]
+    # (a step on a kept K starts at its RHS-only kernel instead)
+    starts = [i for i, r in enumerate(rows) if r[2].startswith(("k_assemble", "k_amg_rhs"))]
     steps = []
     for a, b in zip(starts, starts[1:] + [len(rows)]):
         ks = rows[a:b]
