@@ -70,7 +70,12 @@ extern "C" {
                                    f64 pivots D̃_i = D_i − Σ_{j<i} A_ij D̃_j⁻¹ A_ijᵀ — in
                                    the same chain-piece multicolour order as MFEA_PC_SOR */
 
-/* Every preconditioner stops on the norm mfea_solve_opts.norm selects. */
+/* Every preconditioner stops on the norm mfea_solve_opts.norm selects.
+ * One-partition MFEA_PC_GAMG solves on MFEA_NORM_UNPRECONDITIONED test ‖r‖₂
+ * of a batch's last update directly: n iterations cost n V-cycles, where
+ * MFEA_NORM_PRECONDITIONED (its test needs M⁻¹r) costs n + 1; the results
+ * have the same bits (option "amg_close", read-only "amg_last_cycles" and
+ * "amg_close_hits": mfea_debug.h). */
 /* stopping norm (mfea_solve_opts.norm) */
 #define MFEA_NORM_UNPRECONDITIONED 0 /* ‖r‖₂ ≤ rtol·‖b‖₂  (SciPy cg; the metric)      */
 #define MFEA_NORM_PRECONDITIONED 1   /* ‖z‖₂ ≤ rtol·‖M⁻¹b‖₂ (PETSc KSPCG default)     */

@@ -113,10 +113,29 @@ int mfea_debug_floating(mfea_handle* h, uint8_t* out);
  *                        the build and asm_kernel hold (only the RHS is formed), and keep the
  *                        GAMG hierarchy's values while K, the plan, the floating mask, reg
  *                        and ω hold (1; 0: assemble and set up every step).  Every other
- *                        option set drops both, but phase_times and run_register.
+ *                        option set drops both, but phase_times, run_register, amg_close and amg_start.
  *                        Read-only totals since mfea_create: "op_kept_steps" (steps that
  *                        skipped the assembly), "amg_setup_kept" (solves that skipped the
  *                        numeric setup) — mfea.h mfea_step, DESIGN.md §4.7
+ *   "amg_close" 0|1      MFEA_PC_GAMG, one partition, MFEA_NORM_UNPRECONDITIONED: every chunk of
+ *                        the solve ends with a closing check — ‖r‖² of its last update, summed
+ *                        as the next update would sum it — and the planned batch is one
+ *                        (V-cycle, w = A u, update) group shorter: a solve of n iterations
+ *                        applies n V-cycles, not n + 1 (1; 0: the batch ends with the update
+ *                        that finds the convergence).  Every result has the same bits either
+ *                        way.  Keeps K and the hierarchy's values, like phase_times.
+ *                        The preconditioned norm, SOR / ICC and the partitioned solves run
+ *                        as with 0.  Read-only: "amg_last_cycles" (preconditioner
+ *                        applications the last one-partition GAMG / SOR / ICC solve queued,
+ *                        the early-exiting ones of an overlong plan included),
+ *                        "amg_close_hits" (total since mfea_create of solves that ended at
+ *                        a closing check) — DESIGN.md §4.8
+ *   "amg_start" 0|1      MFEA_PC_GAMG, one partition, a solve that keeps the hierarchy's values
+ *                        (keep_operator) and still has its RHS to form: the RHS, the CG's start
+ *                        state and level-0 b as one launch, k_amg_start (1), instead of
+ *                        k_amg_rhs, k_cg_init_finalize and k_amg_cg_init (0); the same bits.
+ *                        Keeps K and the hierarchy's values when set.  Read-only
+ *                        "amg_start_fused": solves that started with k_amg_start
  * Read-only: "sweep_colors", "sweep_pieces" (the last SOR / ICC plan), "asm_colours"
  * (the element colouring's colours once asm_kernel 1 or 2 has run; 0 before).
  * Options that change the symbolic layout rebuild it at the next call. */

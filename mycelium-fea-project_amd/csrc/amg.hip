@@ -1393,6 +1393,61 @@ __global__ __launch_bounds__(kBlock) void k_amg_cg_init(AmgLevD L0, AmgCg cg, co
   vcycle_entry<ND>(L0, cg, i, r);
 }
 
+// inv[row0[i]] = i: the free Pattern row → its level-0 row (−1 set before)
+__global__ __launch_bounds__(kBlock) void k_amg_row0_inverse(AmgCg cg, int32_t* __restrict__ inv) {
+  const int64_t i = cg.lo + (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i < cg.hi) inv[cg.row0[i]] = (int32_t)i;
+}
+
+// The start of a solve on kept hierarchy values as ONE launch (option
+// amg_start): k_amg_rhs's grid over the Pattern rows with its row body and
+// block_publish — b and ‖b‖² keep their bits — each free row also doing
+// k_amg_cg_init's work for its level-0 row inv[row] (the same r, the same
+// vcycle_entry: level 0's D⁻¹ and ω must be current, i.e. the setup kept),
+// and the reduction's last block k_cg_init_finalize's: the state, and the
+// zeroing of the partial buffers.
+template <int ND>
+__global__ __launch_bounds__(kBlock) void k_amg_start(SellOp op, const uint8_t* __restrict__ code, double dy_top,
+                                                      double dy_bot, CgVecs v, double* partials, unsigned* ticket,
+                                                      double* red_out, AmgLevD L0, AmgCg cg,
+                                                      const int32_t* __restrict__ inv, double rtol, double atol,
+                                                      int norm, int max_it, double reg, SolveState* st,
+                                                      double* zero, int64_t nzero) {
+  const int64_t row = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  double acc[2] = {0.0, 0.0};
+  if (row < op.nf) {
+    double b[3];
+    amg_rhs_row(op, code, dy_top, dy_bot, row, b);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      v.r[0][3 * row + a] = b[a];
+      acc[0] = fma(b[a], b[a], acc[0]);
+    }
+    const int64_t i = inv[row];
+    if (i >= cg.lo && i < cg.hi) {
+      double r[ND], z[ND];
+#pragma unroll
+      for (int a = 0; a < ND; ++a) {
+        r[a] = b[a];
+        z[a] = 0.0;
+      }
+      vstore<ND>(cg.r, i, r);
+      vstore<ND>(cg.x, i, z);
+      vstore<ND>(cg.p, i, z);
+      vstore<ND>(cg.s, i, z);
+      vcycle_entry<ND>(L0, cg, i, r);
+    }
+  } else if (row < op.N) {
+    const uint8_t c = code[row];
+    v.x[3 * row] = 0.0;
+    v.x[3 * row + 1] = c == 3 ? 0.0 : (c == 2 ? dy_bot : dy_top);
+    v.x[3 * row + 2] = 0.0;
+  }
+  if (!block_publish<2>(acc, partials, ticket, red_out)) return;
+  for (int64_t k = threadIdx.x; k < nzero; k += kBlock) zero[k] = 0.0;
+  if (threadIdx.x == 0) cg_state_init(st, red_out[0], red_out[1], rtol, atol, norm, max_it, reg);
+}
+
 template <int ND, bool FIRST, int BS, bool DIST, int KW = 1>
 __global__ __launch_bounds__(BS) void k_amg_cg_w(int j, AmgLevD L0, AmgCg cg, Slot* slots, double* part,
                                                  AmgDist d) {
@@ -1443,6 +1498,27 @@ __global__ __launch_bounds__(BS) void k_amg_cg_w(int j, AmgLevD L0, AmgCg cg, Sl
     s0.pad = 0;
     slots[0] = s0;
   }
+}
+
+// The closing check of a chunk (cg.hip k_cg_advance): block partials of ‖r‖²
+// alone, without the V-cycle and w = A u whose launch would form them next.
+// The w kernel's block size, grid, row mapping, per-thread row order and fma
+// chain: partial b is bit for bit the acc[2] partial of the next w launch.
+// cpart: a buffer of its own, [4][kCgMaxG] as one parity of `part` (the w
+// and update launches of a continuing chunk find theirs untouched).
+template <int ND, int BS>
+__global__ __launch_bounds__(BS) void k_amg_rnorm(AmgCg cg, double* cpart) {
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  const int64_t stride = (int64_t)gridDim.x * BS;
+  const int lane = threadIdx.x & 63;
+  for (int64_t i = cg.lo64() + xcd_block() * BS + threadIdx.x; i - lane < cg.hi; i += stride) {
+    if (i < cg.lo || i >= cg.hi) continue;
+    double r[ND];
+    vload<ND>(cg.r, i, r);
+#pragma unroll
+    for (int a = 0; a < ND; ++a) acc[2] = fma(r[a], r[a], acc[2]);
+  }
+  store_block_partial<BS>(acc, cpart);
 }
 
 // Partitioned: this rank's sums (its w kernel's block partials in block
@@ -2027,6 +2103,25 @@ void launch_amg_cg_init(hipStream_t s, int nd, const AmgLevD& L0, const AmgCg& c
   else hipLaunchKernelGGL(k_amg_cg_init<3>, rows_grid(cg.hi - cg.lo), dim3(kBlock), 0, s, L0, cg, b_row);
 }
 
+void launch_amg_row0_inverse(hipStream_t s, const AmgCg& cg, int32_t* inv, int64_t n_rows) {
+  (void)hipMemsetAsync(inv, 0xff, (size_t)n_rows * sizeof(int32_t), s);  // −1
+  if (cg.hi <= cg.lo) return;
+  hipLaunchKernelGGL(k_amg_row0_inverse, rows_grid(cg.hi - cg.lo), dim3(kBlock), 0, s, cg, inv);
+}
+
+void launch_amg_start(hipStream_t s, int nd, const SellOp& op, const uint8_t* code, double dy_top, double dy_bot,
+                      const CgVecs& v, double* partials, unsigned* ticket, double* red_out, const AmgLevD& L0,
+                      const AmgCg& cg, const int32_t* inv, double rtol, double atol, int norm, int max_it,
+                      double reg, SolveState* st, double* zero, int64_t nzero) {
+  const dim3 grid((unsigned)grid_rows(op.N > 0 ? op.N : 1));  // k_amg_rhs's (launch_cg_rhs)
+  if (nd == 2)
+    hipLaunchKernelGGL(k_amg_start<2>, grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials, ticket,
+                       red_out, L0, cg, inv, rtol, atol, norm, max_it, reg, st, zero, nzero);
+  else
+    hipLaunchKernelGGL(k_amg_start<3>, grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials, ticket,
+                       red_out, L0, cg, inv, rtol, atol, norm, max_it, reg, st, zero, nzero);
+}
+
 template <int ND, int BS>
 static void w_bs(hipStream_t s, int j, bool first, const AmgLevD& L0, const AmgCg& cg, Slot* slots,
                  double* part, const AmgDist* d) {
@@ -2060,6 +2155,25 @@ void launch_amg_cg_w(hipStream_t s, int nd, int j, bool first, const AmgLevD& L0
                      Slot* slots, double* part, const AmgDist* d) {
   if (nd == 2) w_nd<2>(s, j, first, L0, cg, slots, part, d);
   else w_nd<3>(s, j, first, L0, cg, slots, part, d);
+}
+
+// the w kernel's launch geometry (w_nd / w_bs), so the partials match its own
+template <int ND>
+static void rnorm_nd(hipStream_t s, const AmgCg& cg, double* cpart) {
+  const dim3 g((unsigned)amg_w_grid(cg));
+  switch (amg_w_block(cg)) {
+    case 512: hipLaunchKernelGGL((k_amg_rnorm<ND, 512>), g, dim3(512), 0, s, cg, cpart); break;
+    case 576: hipLaunchKernelGGL((k_amg_rnorm<ND, 576>), g, dim3(576), 0, s, cg, cpart); break;
+    case 640: hipLaunchKernelGGL((k_amg_rnorm<ND, 640>), g, dim3(640), 0, s, cg, cpart); break;
+    case 704: hipLaunchKernelGGL((k_amg_rnorm<ND, 704>), g, dim3(704), 0, s, cg, cpart); break;
+    case 768: hipLaunchKernelGGL((k_amg_rnorm<ND, 768>), g, dim3(768), 0, s, cg, cpart); break;
+    case 1024: hipLaunchKernelGGL((k_amg_rnorm<ND, 1024>), g, dim3(1024), 0, s, cg, cpart); break;
+    default: hipLaunchKernelGGL((k_amg_rnorm<ND, kCgBS>), g, dim3(kCgBS), 0, s, cg, cpart); break;
+  }
+}
+void launch_amg_rnorm(hipStream_t s, int nd, const AmgCg& cg, double* cpart) {
+  if (nd == 2) rnorm_nd<2>(s, cg, cpart);
+  else rnorm_nd<3>(s, cg, cpart);
 }
 
 void launch_amg_gsum(hipStream_t s, const AmgCg& cg, const double* part_q, const AmgDist& d, int q) {

@@ -105,10 +105,14 @@ struct Part {
   PartPlan plan;  // partitioned only
   DevBuf<double> xyz_d, val, diag, x, r, p, q, dinv, stress, partials, red;
   DevBuf<double> cg_r1, cg_s0, cg_s1, cg_w0, cg_w1;  // CG-CG double buffers (r0 = r)
-  DevBuf<double> cg_part;                            // CG-CG block partials, 2 parities
+  DevBuf<double> cg_part;                            // CG-CG block partials, 2 parities; a third buffer:
+                                                     // the closing check's (k_amg_rnorm)
   DevBuf<int32_t> slice_ptr, row_len, s_col, s_elem, e2n_d;
   DevBuf<uint8_t> active, code, elem_own;
   DevBuf<int32_t> fail_list;  // (owned) elements failed in the last post (any order)
+  DevBuf<int32_t> amg_inv;    // Pattern row → level-0 row (k_amg_start), for the plan below
+  int64_t amg_inv_gen = -1;
+  const int32_t* amg_inv_row0 = nullptr;
   DevBuf<unsigned> fail_cnt;
   DevBuf<unsigned> tickets;
   // wave-local lane operator (ell.hip); ell_ok = false → SELL kernel
@@ -333,6 +337,17 @@ struct mfea_handle {
   int last_precond = -1;          // the last solve's preconditioner kind
   int64_t op_kept_steps = 0;      // read-only option: steps that skipped the assembly
   int64_t amg_setup_kept = 0;     // read-only option: solves that skipped the numeric setup
+  // One-partition GAMG solves on the unpreconditioned norm end every chunk
+  // with a closing check (enqueue_amg_chunk): the planned batch is one group
+  // shorter, the converging update's V-cycle and w = A u are not run.  0: the
+  // batch ends with the update that finds the convergence, as before.
+  int opt_amg_close = 1;
+  int64_t amg_close_hits = 0;     // read-only option: solves that ended at the closing check
+  int amg_last_cycles = 0;        // read-only option: preconditioner applications the last GAMG solve queued
+  // A solve on kept hierarchy values starts with ONE launch (k_amg_start: the
+  // RHS, the CG's state and level-0 b) instead of three.  0: the three.
+  int opt_amg_start = 1;
+  int64_t amg_start_fused = 0;    // read-only option: solves that started with k_amg_start
   bool setup_skipped = false;     // the last solve did (phase times: t_setup_ms = 0)
   Material graph_batch_mat{};     // the material graph_batch's post kernels were captured with
   bool asm_pending = false;  // mfea_step deferred its assembly to solve_amg
@@ -618,7 +633,7 @@ int upload_part(mfea_handle* h, Part& pt, bool dm) {
   HIPC(pt.cg_s1.alloc(3 * N));
   HIPC(pt.cg_w0.alloc(3 * N));
   HIPC(pt.cg_w1.alloc(3 * N));
-  HIPC(pt.cg_part.alloc(2 * 4 * kCgMaxPartials));
+  HIPC(pt.cg_part.alloc(3 * 4 * kCgMaxPartials));
   HIPC(pt.dinv.alloc(6 * N));
   HIPC(pt.stress.alloc(E));
   HIPC(pt.partials.alloc(4 * (maxg + 16)));
@@ -1151,13 +1166,16 @@ int drive_planned(mfea_handle* h, int chunk, int max_it, int expected, Enqueue&&
 // ≈ 13 µs) per `big` iterations instead of per `small`, while a batch never
 // overshoots the expected count by more than small − 1 — then short chunks
 // one at a time until the device reports done.  enqueue(size) queues one.
+// zero_ok (chunks that end with a closing check, enqueue_amg_chunk): a batch
+// of no updates is queued as one chunk of length 0 — the check alone.
 template <class Enqueue, class After = NoEpilogue>
 int drive_sized(mfea_handle* h, int big, int small, int max_it, int expected, Enqueue&& enqueue,
-                SolveState* out, After&& after = After{}, bool exact_rem = false) {
+                SolveState* out, After&& after = After{}, bool exact_rem = false, bool zero_ok = false) {
   hipStream_t s = h->stream;
   volatile SolveState* hs = h->h_state;
   hs[0].done = 0;
-  const int need = std::max(1, expected + 1);  // updates the batch assumes, as drive_planned
+  const int need = std::max(zero_ok ? 0 : 1, expected + 1);  // updates the batch assumes, as drive_planned
+  if (need == 0) RC(enqueue(0));
   const int nbig = big > small ? need / big : 0;
   const int rem = need - nbig * big;
   const int nsmall = (rem + small - 1) / small;
@@ -2090,7 +2108,15 @@ int enqueue_amg_dist_chunk(mfea_handle* h, int chunk) {
 // knowing whether the solve converged and no chunk of early-exiting launches
 // is queued after the converging update (each gated launch still costs
 // ≈ 4 µs).  update 0 runs before the first chunk (solve_amg).
-void enqueue_amg_chunk(mfea_handle* h, Part& pt, int chunk) {
+//
+// close (solve_amg's amg_close): the chunk ends … update, k_amg_rnorm,
+// advance.  The chunk's last update has moved r and only the NEXT update
+// would test it, behind a V-cycle and a w = A u that nothing else needs when
+// it has converged: the advance kernel tests ‖r‖² from k_amg_rnorm's partials
+// instead (k_cg_advance's closing form), so a planned batch of iters − 1
+// groups ends the solve — iters V-cycles in all, not iters + 1.  chunk may
+// then be 0: the entry's update 0, the closing check, nothing else.
+void enqueue_amg_chunk(mfea_handle* h, Part& pt, int chunk, bool close) {
   hipStream_t s = h->stream;
   const int nd = pt.amg.nd;
   const AmgLevD& L0 = pt.amg_lev[0];
@@ -2105,7 +2131,9 @@ void enqueue_amg_chunk(mfea_handle* h, Part& pt, int chunk) {
     launch_amg_cg_w(s, nd, j, false, L0, pt.amg_cg, pt.slots.ptr, pt.cg_part.ptr);
     launch_amg_cg_update(s, nd, j + 1, L0, pt.amg_cg, pt.slots.ptr, pt.state.ptr, pt.cg_part.ptr);
   }
-  launch_cg_advance(s, chunk, pt.slots.ptr, pt.state.ptr, pt.mirror, 1);
+  if (close) launch_amg_rnorm(s, nd, pt.amg_cg, cg_part_buf(pt, 2));
+  launch_cg_advance(s, chunk, pt.slots.ptr, pt.state.ptr, pt.mirror, 1, close ? cg_part_buf(pt, 2) : nullptr,
+                    close ? (int)amg_w_grid(pt.amg_cg) : 0);
 }
 
 // hierarchy values for the current K (the per-solve numeric setup)
@@ -2151,11 +2179,12 @@ int enqueue_post_work(mfea_handle* h, double max_strain);
 
 // The solve's entry behind the setup: level-0 b from the CG's r, the first
 // preconditioner application, w = A u, update 0 (solve_amg)
-void enqueue_amg_entry(mfea_handle* h, Part& pt) {
+// (skip_init: k_amg_start has done launch_amg_cg_init's work, solve_amg)
+void enqueue_amg_entry(mfea_handle* h, Part& pt, bool skip_init = false) {
   hipStream_t s = h->stream;
   const int nd = pt.amg.nd;
   const AmgLevD& L0 = pt.amg_lev[0];
-  launch_amg_cg_init(s, nd, L0, pt.amg_cg, cg_vecs(pt).r[0]);
+  if (!skip_init) launch_amg_cg_init(s, nd, L0, pt.amg_cg, cg_vecs(pt).r[0]);
   launch_precond(h, pt, nullptr);
   launch_amg_cg_w(s, nd, 0, true, L0, pt.amg_cg, pt.slots.ptr, pt.cg_part.ptr);
   launch_amg_cg_update(s, nd, 0, L0, pt.amg_cg, pt.slots.ptr, pt.state.ptr, pt.cg_part.ptr);  // update 0
@@ -2214,18 +2243,20 @@ uint64_t amg_setup_key(mfea_handle* h, Part& pt, double reg) {
 // the one with them; nothing at all where no head / entry / tail rides along
 int launch_amg_setup_graph(mfea_handle* h, Part& pt, double reg, uint64_t k0, bool keep, bool entry = false,
                            const mfea_solve_opts* head = nullptr, const mfea_solve_opts* start = nullptr,
-                           int tail = 0, int tag = 0) {
+                           int tail = -1, int tag = 0, bool close = false, bool skip_init = false) {
   hipStream_t s = h->stream;
   uint64_t k = k0;
   const int form = keep ? 1 : 0;
   k = fnv1a(k, &form, sizeof form);
-  if (keep && !entry && !head && !start && tail <= 0) return 0;
+  if (keep && !entry && !head && !start && tail < 0) return 0;
   if (entry) {
     const CgVecs v = cg_vecs(pt);
     const void* eptrs[4] = {v.r[0], pt.slots.ptr, pt.state.ptr, pt.cg_part.ptr};
     k = fnv1a(k, eptrs, sizeof eptrs);
     k = fnv1a(k, &pt.amg_cg, sizeof pt.amg_cg);
     k = fnv1a(k, &pt.amg_kind, sizeof pt.amg_kind);
+    const int si = skip_init ? 1 : 0;
+    k = fnv1a(k, &si, sizeof si);
   }
   if (start) {  // the CG start (k_cg_init_finalize) at the graph's head
     const double sd[3] = {start->rtol, start->atol, start->reg};
@@ -2246,9 +2277,10 @@ int launch_amg_setup_graph(mfea_handle* h, Part& pt, double reg, uint64_t k0, bo
     k = fnv1a(k, &h->mat, sizeof h->mat);
     k = fnv1a(k, &pt.tickets.ptr, sizeof pt.tickets.ptr);
   }
-  if (tail > 0) {
+  if (tail >= 0) {
     // the step's whole GPU work but the assembly: setup, entry, the planned
-    // batch of `tail` iterations, the finish, the post (mfea_step, batch_graph)
+    // batch of `tail` iterations (with the closing check, `tag` tells the two
+    // forms apart, it may be 0), the finish, the post (mfea_step, batch_graph)
     k = fnv1a(k ^ 0xc0b0, &tail, sizeof tail);
     k = fnv1a(k, &tag, sizeof tag);
     k = fnv1a(k, &h->spec_strain, sizeof h->spec_strain);
@@ -2267,8 +2299,8 @@ int launch_amg_setup_graph(mfea_handle* h, Part& pt, double reg, uint64_t k0, bo
         launch_cg_init_finalize(s, pt.red.ptr, start->rtol, start->atol, start->norm, start->max_it, start->reg,
                                 pt.state.ptr, pt.cg_part.ptr, 2 * 4 * kCgMaxPartials);
       if (!keep) enqueue_amg_setup(h, pt, reg);
-      enqueue_amg_entry(h, pt);
-      enqueue_amg_chunk(h, pt, tail);
+      enqueue_amg_entry(h, pt, skip_init);
+      enqueue_amg_chunk(h, pt, tail, close);
       launch_amg_finish(s, pt.amg.nd, pt.amg_cg, pt.x.ptr);
       const int prc = enqueue_post_work(h, h->spec_strain);
       const hipError_t ec = hipStreamEndCapture(s, &g);
@@ -2296,7 +2328,7 @@ int launch_amg_setup_graph(mfea_handle* h, Part& pt, double reg, uint64_t k0, bo
       launch_cg_init_finalize(s, pt.red.ptr, start->rtol, start->atol, start->norm, start->max_it, start->reg,
                               pt.state.ptr, pt.cg_part.ptr, 2 * 4 * kCgMaxPartials);
     if (!keep) enqueue_amg_setup(h, pt, reg);
-    if (entry) enqueue_amg_entry(h, pt);
+    if (entry) enqueue_amg_entry(h, pt, skip_init);
     HIPC(hipStreamEndCapture(s, &g));
     const hipError_t e = hipGraphInstantiate(&gs, g, nullptr, nullptr, 0);
     (void)hipGraphDestroy(g);
@@ -2351,25 +2383,50 @@ int solve_amg(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opt
   RC(phase_event(h, h->ev[1], s));
   // the CG start inside the setup graph when no phase event separates them
   const bool start_in_graph = h->opt_graph && h->opt_graph_start && !h->opt_phase_times && !head;
+  // kept values (level 0's D⁻¹ and ω are current) and an RHS still to form:
+  // the RHS, the CG's start and level-0 b as one launch (option amg_start)
+  bool fused_start = false;
   if (!head) {
     // (mfea_step's assembly formed it for these displacements: AsmRhs)
     const bool rhs_done = h->rhs_fused && h->rhs_dy[0] == dy_top && h->rhs_dy[1] == dy_bot;
     h->rhs_fused = false;
-    if (!rhs_done)
-      launch_cg_rhs(s, op, pt.code.ptr, dy_top, dy_bot, o->reg, 2, v, pt.partials.ptr, tix(pt, 0), pt.red.ptr);
-    if (!start_in_graph)
-      launch_cg_init_finalize(s, pt.red.ptr, o->rtol, o->atol, o->norm, o->max_it, o->reg, pt.state.ptr,
-                              pt.cg_part.ptr, 2 * 4 * kCgMaxPartials);
+    fused_start = h->opt_amg_start && keep && !rhs_done;
+    if (fused_start) {
+      if (pt.amg_inv_gen != pt.amg_gen || pt.amg_inv_row0 != pt.amg_cg.row0) {
+        HIPC(pt.amg_inv.alloc(pt.P.n_nodes > 0 ? pt.P.n_nodes : 1));
+        launch_amg_row0_inverse(s, pt.amg_cg, pt.amg_inv.ptr, pt.P.n_nodes);
+        pt.amg_inv_gen = pt.amg_gen;
+        pt.amg_inv_row0 = pt.amg_cg.row0;
+      }
+      launch_amg_start(s, nd, op, pt.code.ptr, dy_top, dy_bot, v, pt.partials.ptr, tix(pt, 0), pt.red.ptr,
+                       pt.amg_lev[0], pt.amg_cg, pt.amg_inv.ptr, o->rtol, o->atol, o->norm, o->max_it, o->reg,
+                       pt.state.ptr, pt.cg_part.ptr, 2 * 4 * kCgMaxPartials);
+      ++h->amg_start_fused;
+    } else {
+      if (!rhs_done)
+        launch_cg_rhs(s, op, pt.code.ptr, dy_top, dy_bot, o->reg, 2, v, pt.partials.ptr, tix(pt, 0), pt.red.ptr);
+      if (!start_in_graph)
+        launch_cg_init_finalize(s, pt.red.ptr, o->rtol, o->atol, o->norm, o->max_it, o->reg, pt.state.ptr,
+                                pt.cg_part.ptr, 2 * 4 * kCgMaxPartials);
+    }
   }
   RC(phase_event(h, h->ev[2], s));
   // (phase times: the setup's end is an event between the setup and the entry)
   const bool entry = h->opt_graph && h->opt_setup_entry && !h->opt_phase_times;
-  const int tag = -1000 - (int)(pt.amg_gen % 1000000);
+  // the closing check (enqueue_amg_chunk): GAMG on the unpreconditioned norm
+  // — PETSc's preconditioned norm needs M r for its test, and the sweep
+  // preconditioners (SOR, ICC) keep the path they were measured on
+  const bool close = h->opt_amg_close && o->norm == MFEA_NORM_UNPRECONDITIONED && pt.amg_kind == MFEA_PC_GAMG;
+  // (every cached chunk graph is tagged: the two chunk forms never mix)
+  // (−4,000,000: below the partitioned forms' ranges, −2,000,000 − x and −3,000,000 − x)
+  const int tag = -1000 - (int)(pt.amg_gen % 1000000) - (close ? 4000000 : 0);
   // the converging update is iteration `iters`; update 0 ran in the entry, so
-  // `expected` more updates = expected / chunk chunks (drive_planned adds one
-  // for the update it assumes the chunk starts with: pass expected − 1)
-  const int expected = std::max(0, std::min(o->max_it, pt.amg_last_iters > 0 ? pt.amg_last_iters : 16) - 1);
-  const int need = std::max(1, expected + 1);
+  // `iters` more groups (V-cycle, w, update) reach it: need.  With the closing
+  // check the batch ends one group earlier, behind update iters − 1, and its
+  // check finds what update `iters` would have (need may then be 0)
+  const int planned = std::min(o->max_it, pt.amg_last_iters > 0 ? pt.amg_last_iters : 16);
+  const int need = close ? std::max(0, planned - 1) : std::max(1, planned);
+  int cycles = 1;  // preconditioner applications queued: the entry's, then one per group
   // mfea_step: the planned batch, the finish and the post as ONE graph of the
   // batch's exact length (option batch_graph), behind the setup in the same
   // graph (option combo_graph)
@@ -2389,7 +2446,8 @@ int solve_amg(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opt
     const bool split = combo && !keep && h->opt_keep_operator && !head;
     if (split) RC(launch_amg_setup_graph(h, pt, o->reg, skey, false));
     RC(launch_amg_setup_graph(h, pt, o->reg, skey, keep || split, entry, head ? o : nullptr,
-                              start_in_graph ? o : nullptr, combo ? need : 0, tag));
+                              start_in_graph && !fused_start ? o : nullptr, combo ? need : -1, tag, close,
+                              fused_start));
   } else if (!keep) {
     enqueue_amg_setup(h, pt, o->reg);
   }
@@ -2397,7 +2455,7 @@ int solve_amg(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opt
   if (!entry) {
     RC(phase_event(h, h->ev_setup, s));
     h->ev_setup_used = true;
-    enqueue_amg_entry(h, pt);
+    enqueue_amg_entry(h, pt, fused_start);
   }
   HIPC(hipGetLastError());
   const bool no_graph = !h->opt_graph;
@@ -2411,9 +2469,10 @@ int solve_amg(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opt
     return spec_post(h);  // (mfea_step: the post behind the batch, one wait for both)
   };
   if (no_graph) {
-    rc = drive_planned(h, chunk, o->max_it, expected,
+    rc = drive_planned(h, chunk, o->max_it, need - 1,
                        [&]() -> int {
-                         enqueue_amg_chunk(h, pt, chunk);
+                         enqueue_amg_chunk(h, pt, chunk, close);
+                         cycles += chunk;
                          HIPC(hipGetLastError());
                          return 0;
                        },
@@ -2422,7 +2481,7 @@ int solve_amg(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opt
     auto capture = [&](hipGraphExec_t* ge, int n) -> int {
       hipGraph_t g;
       HIPC(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-      enqueue_amg_chunk(h, pt, n);
+      enqueue_amg_chunk(h, pt, n, close);
       HIPC(hipStreamEndCapture(s, &g));
       hipError_t e = hipGraphInstantiate(ge, g, nullptr, nullptr, 0);
       (void)hipGraphDestroy(g);
@@ -2477,7 +2536,7 @@ int solve_amg(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opt
       if (!combo && h->graph_batch[need] == nullptr) {
         hipGraph_t g;
         HIPC(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        enqueue_amg_chunk(h, pt, need);
+        enqueue_amg_chunk(h, pt, need, close);
         launch_amg_finish(s, nd, pt.amg_cg, pt.x.ptr);
         const int prc = enqueue_post_work(h, h->spec_strain);
         const hipError_t ec = hipStreamEndCapture(s, &g);
@@ -2490,25 +2549,31 @@ int solve_amg(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opt
       rc = drive_batch(h, chunk, o->max_it, need,
                        [&]() -> int {
                          if (!combo) HIPC(hipGraphLaunch(h->graph_batch[need], s));  // (combo: launched with the setup)
+                         cycles += need;
                          return 0;
                        },
                        [&](int n) -> int {
                          HIPC(hipGraphLaunch(h->graph, s));
-                         (void)n;
+                         cycles += n;
                          return 0;
                        },
                        &fin, finish, combo);
     } else {
-      if (exact_rem && h->graph_rem[rem] == nullptr) RC(capture(&h->graph_rem[rem], rem));
-      rc = drive_sized(h, big, chunk, o->max_it, expected,
+      // (need 0: the closing check alone, a chunk of length 0 among the remainders)
+      const int odd = need == 0 ? 0 : rem;
+      if ((exact_rem || need == 0) && h->graph_rem[odd] == nullptr) RC(capture(&h->graph_rem[odd], odd));
+      rc = drive_sized(h, big, chunk, o->max_it, need - 1,
                        [&](int n) -> int {
                          HIPC(hipGraphLaunch(n == chunk ? h->graph : n == big ? h->graph_big : h->graph_rem[n], s));
+                         cycles += n;
                          return 0;
                        },
-                       &fin, finish, exact_rem);
+                       &fin, finish, exact_rem, close);
     }
   }
   if (rc) return rc;
+  h->amg_last_cycles = cycles;
+  if (fin.status == 0 && fin.closed) ++h->amg_close_hits;
   if (fin.status != 0) RC(spec_undo(h));
   clk.lap("solve (setup + iterations)", fin.iters);
   if (fin.status != 0 && pt.amg_reused) {
@@ -2530,7 +2595,7 @@ int solve_amg(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opt
     // solve's time per iteration; once that rent adds up to the last build's
     // time, or one solve needs far more (amg_rebuild_pct), rebuild
     const double t_it = std::chrono::duration<double>(std::chrono::steady_clock::now() - drive_t0).count() /
-                        std::max<int64_t>(1, fin.iters + 1);
+                        std::max<int64_t>(1, fin.closed ? fin.iters : fin.iters + 1);  // (the cycles it took)
     if (fin.iters > pt.amg_build_iters) pt.amg_excess_s += (fin.iters - pt.amg_build_iters) * t_it;
     const bool rent_due = h->opt_amg_rebuild_rent > 0 &&
                           pt.amg_excess_s >= pt.amg_build_s * h->opt_amg_rebuild_rent / 100.0;
@@ -3825,7 +3890,10 @@ int mfea_step(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opt
     ++h->op_kept_steps;
     h->rhs_fused = false;
     RC(phase_event(h, h->ev[0], s));
-    if (fuse_rhs) {
+    // (GAMG with option amg_start: left to solve_amg, which knows whether the
+    // hierarchy's values are kept too and then forms the RHS in k_amg_start —
+    // the same kernel from there otherwise)
+    if (fuse_rhs && !(h->opt_amg_start && o.precond == MFEA_PC_GAMG)) {
       Part& pt = part0(h);
       launch_cg_rhs(s, sell_op(pt), pt.code.ptr, dy_top, dy_bot, o.reg, 2, cg_vecs(pt), pt.partials.ptr, tix(pt, 0),
                     pt.red.ptr);
@@ -4685,10 +4753,20 @@ int mfea_set_option(mfea_handle* h, const char* name, int64_t value) {
     if (value != 0 && value != 1) return fail(MFEA_EINVAL, "keep_operator: 0 or 1");
     h->opt_keep_operator = (int)value;
   }
+  else if (n == "amg_close") {
+    if (value != 0 && value != 1) return fail(MFEA_EINVAL, "amg_close: 0 or 1");
+    h->opt_amg_close = (int)value;
+  }
+  else if (n == "amg_start") {
+    if (value != 0 && value != 1) return fail(MFEA_EINVAL, "amg_start: 0 or 1");
+    h->opt_amg_start = (int)value;
+  }
   else return fail(MFEA_EINVAL, "unknown option " + n);
   // kept K / hierarchy values: dropped by every option but the few that
   // cannot change a value (conservative: most options only change launches)
-  if (n != "phase_times" && n != "run_register" && !(n == "keep_operator" && value == 1)) drop_kept(h);
+  if (n != "phase_times" && n != "run_register" && !(n == "keep_operator" && value == 1) &&
+      n != "amg_close" && n != "amg_start")
+    drop_kept(h);
   destroy_graph(h);  // captured graphs hold the old geometry
   if (rebuild) {
     if (!h->dirty && h->Ecount) {  // keep the current activity across the rebuild
@@ -4898,6 +4976,11 @@ int mfea_get_option(mfea_handle* h, const char* name, int64_t* value) {
   else if (n == "keep_operator") *value = h->opt_keep_operator;
   else if (n == "op_kept_steps") *value = h->op_kept_steps;    // read-only: steps that skipped the assembly
   else if (n == "amg_setup_kept") *value = h->amg_setup_kept;  // read-only: solves that skipped the numeric setup
+  else if (n == "amg_close") *value = h->opt_amg_close;
+  else if (n == "amg_start") *value = h->opt_amg_start;
+  else if (n == "amg_start_fused") *value = h->amg_start_fused;  // read-only: solves that started with k_amg_start
+  else if (n == "amg_close_hits") *value = h->amg_close_hits;    // read-only: solves ended by the closing check
+  else if (n == "amg_last_cycles") *value = h->amg_last_cycles;  // read-only: V-cycle applications the last solve queued
   else if (n == "asm_colours") {
     *value = 0;
     for (auto& pp : h->parts) *value = std::max<int64_t>(*value, pp->ec_state > 0 ? pp->ec.colors : 0);

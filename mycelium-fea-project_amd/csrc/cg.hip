@@ -152,33 +152,8 @@ __global__ __launch_bounds__(kBlock) void k_amg_rhs(SellOp op, const uint8_t* __
   const int64_t row = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   double acc[2] = {0.0, 0.0};
   if (row < op.nf) {
-    const int64_t base = (int64_t)op.slice_ptr[row >> 6] * 64 + (row & 63);
-    const int len = op.row_len[row];
-    const int64_t G = op.G;
-    double kx = 0.0, ky = 0.0, kz = 0.0;
-    constexpr int U = 4;
-    for (int k0 = 0; k0 < len; k0 += U) {
-      int64_t idx[U];
-      int32_t j[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        idx[u] = base + (int64_t)(k0 + u < len ? k0 + u : k0) * 64;
-        j[u] = k0 + u < len ? op.s_col[idx[u]] : 0;
-      }
-      uint8_t c[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) c[u] = k0 + u < len && j[u] >= op.nf ? code[j[u]] : 3;
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        if (c[u] != 3) {  // a known neighbour (3: free or ghost free row, x₀ = 0)
-          const double dy = c[u] == 2 ? dy_bot : dy_top;
-          kx = fma(op.val[1 * G + idx[u]], dy, kx);
-          ky = fma(op.val[3 * G + idx[u]], dy, ky);
-          kz = fma(op.val[4 * G + idx[u]], dy, kz);
-        }
-      }
-    }
-    const double b[3] = {0.0 - kx, 0.0 - ky, 0.0 - kz};
+    double b[3];
+    amg_rhs_row(op, code, dy_top, dy_bot, row, b);
     store3(v.r[0], row, b);
 #pragma unroll
     for (int a = 0; a < 3; ++a) acc[0] = fma(b[a], b[a], acc[0]);
@@ -196,22 +171,7 @@ __global__ void k_cg_init_finalize(const double* red, double rtol, double atol, 
                                    int max_it, double reg, SolveState* st, double* zero, int64_t nzero) {
   for (int64_t k = threadIdx.x; k < nzero; k += blockDim.x) zero[k] = 0.0;
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  const double bb = red[0], zz = red[1];
-  const double ref = norm == 1 ? zz : bb;
-  const double t = rtol * rtol * ref, a2 = atol * atol;
-  st->tol2 = t > a2 ? t : a2;
-  st->rtol2 = rtol * rtol;
-  st->atol2 = a2;
-  st->reg = reg;
-  st->bb0 = bb;
-  st->res0 = ref;
-  st->res_final = ref;
-  st->base = 0;
-  st->max_it = max_it;
-  st->norm = norm;
-  st->done = 0;
-  st->iters = 0;
-  st->status = 0;
+  cg_state_init(st, red[0], red[1], rtol, atol, norm, max_it, reg);
 }
 
 // w₀ = A u₀ and the first partials (γ₀, δ₀, ‖r₀‖², ‖u₀‖²) → parity 0;
@@ -456,10 +416,21 @@ __global__ __launch_bounds__(kCgBS) void k_cg_iter(int j, SellOp op, CgVecs v, S
 // holds the state entering the chunk and its updates wrote slots[2..chunk+1];
 // slots[1] = slots[chunk+1] rolls over.  Either way the first stopped state
 // slots[1 + j] was written by iteration base + j.
-__global__ void k_cg_advance(int chunk, int shift, Slot* slots, SolveState* st, SolveState* host) {
+//
+// Closing form (cpart non-null; shift 1, the unpreconditioned norm): no slot
+// stopped, so the chunk's last update moved x and r and nothing has tested
+// that r yet — the next update would, behind a V-cycle and w = A u that only
+// the continuing solve needs.  ‖r‖² from k_amg_rnorm's partials (the bits
+// that update would reduce) under cg_scalars' test: on convergence the
+// record that update would have left — it applies no x update, so `iters`
+// is its index base + chunk + 1 — else the roll-over, and the next chunk's
+// first update repeats the test as before.
+__global__ void k_cg_advance(int chunk, int shift, Slot* slots, SolveState* st, SolveState* host,
+                             const double* cpart, int cG) {
   if (blockIdx.x != 0) return;
   const int lane = threadIdx.x;
   if (st->done) return;
+  const double rr = cpart ? cg_close_sum(cpart, cG) : 0.0;  // (the whole wave: before any lane leaves)
   const int n = chunk + shift;
   int first = -1;
   for (int j0 = 0; j0 < n && first < 0; j0 += 64) {
@@ -480,6 +451,17 @@ __global__ void k_cg_advance(int chunk, int shift, Slot* slots, SolveState* st, 
     // slots[1]; left as kRun it would apply stale α, β and move x.  The
     // V-cycle / sweep and w launches take no gate: with x, r, p, s frozen
     // they rewrite what they wrote before, capi.hip enqueue_amg_chunk)
+    slots[0].flag = kStop;
+    slots[shift].flag = kStop;
+    *host = *st;
+    return;
+  }
+  if (cpart && st->norm == 0 && cg_close_converged(rr, st->tol2)) {
+    st->iters = st->base + chunk + shift;
+    st->res_final = rr;
+    st->status = 0;
+    st->done = 1;
+    st->closed = 1;
     slots[0].flag = kStop;
     slots[shift].flag = kStop;
     *host = *st;
@@ -549,8 +531,9 @@ void launch_cg_iter(hipStream_t s, int j, const SellOp& op, int precond, const C
   else iter_dispatch<false>(s, j, op, precond, v, slots, st, part, nullptr);
 }
 
-void launch_cg_advance(hipStream_t s, int chunk, Slot* slots, SolveState* st, SolveState* host, int shift) {
-  hipLaunchKernelGGL(k_cg_advance, dim3(1), dim3(64), 0, s, chunk, shift, slots, st, host);
+void launch_cg_advance(hipStream_t s, int chunk, Slot* slots, SolveState* st, SolveState* host, int shift,
+                       const double* cpart, int cG) {
+  hipLaunchKernelGGL(k_cg_advance, dim3(1), dim3(64), 0, s, chunk, shift, slots, st, host, cpart, cG);
 }
 
 }  // namespace mfea

@@ -182,6 +182,64 @@ __device__ __forceinline__ void sym_inverse(const double A[6], double B[6]) {
   B[3] = c11 * id; B[4] = c12 * id; B[5] = c22 * id;
 }
 
+// b = 0 − K_fk x_k of free row `row` for the GAMG solves (k_amg_rhs, cg.hip;
+// k_amg_start, amg.hip).  A row's slots in batches of four: columns, then
+// their codes, then the known couplings; b's terms in slot order.
+__device__ __forceinline__ void amg_rhs_row(const SellOp& op, const uint8_t* __restrict__ code, double dy_top,
+                                            double dy_bot, int64_t row, double b[3]) {
+  const int64_t base = (int64_t)op.slice_ptr[row >> 6] * 64 + (row & 63);
+  const int len = op.row_len[row];
+  const int64_t G = op.G;
+  double kx = 0.0, ky = 0.0, kz = 0.0;
+  constexpr int U = 4;
+  for (int k0 = 0; k0 < len; k0 += U) {
+    int64_t idx[U];
+    int32_t j[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      idx[u] = base + (int64_t)(k0 + u < len ? k0 + u : k0) * 64;
+      j[u] = k0 + u < len ? op.s_col[idx[u]] : 0;
+    }
+    uint8_t c[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) c[u] = k0 + u < len && j[u] >= op.nf ? code[j[u]] : 3;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (c[u] != 3) {  // a known neighbour (3: free or ghost free row, x₀ = 0)
+        const double dy = c[u] == 2 ? dy_bot : dy_top;
+        kx = fma(op.val[1 * G + idx[u]], dy, kx);
+        ky = fma(op.val[3 * G + idx[u]], dy, ky);
+        kz = fma(op.val[4 * G + idx[u]], dy, kz);
+      }
+    }
+  }
+  b[0] = 0.0 - kx;
+  b[1] = 0.0 - ky;
+  b[2] = 0.0 - kz;
+}
+
+// The CG's state at the start of a solve, from the reduced (‖b‖², ‖M⁻¹b‖²)
+// (k_cg_init_finalize, cg.hip; the last block of k_amg_start, amg.hip)
+__device__ __forceinline__ void cg_state_init(SolveState* st, double bb, double zz, double rtol, double atol,
+                                              int norm, int max_it, double reg) {
+  const double ref = norm == 1 ? zz : bb;
+  const double t = rtol * rtol * ref, a2 = atol * atol;
+  st->tol2 = t > a2 ? t : a2;
+  st->rtol2 = rtol * rtol;
+  st->atol2 = a2;
+  st->reg = reg;
+  st->bb0 = bb;
+  st->res0 = ref;
+  st->res_final = ref;
+  st->base = 0;
+  st->max_it = max_it;
+  st->norm = norm;
+  st->done = 0;
+  st->iters = 0;
+  st->status = 0;
+  st->closed = 0;
+}
+
 // ---------------------------------------------------------------------------
 // Shared pieces of the CG iteration kernels (cg.hip: SELL operator, ell.hip:
 // wave-local lanes).
@@ -282,6 +340,29 @@ __device__ __forceinline__ CgScalars cg_scalars(const double S[4], int f0, doubl
   else if (it >= max_it) c.status = kMaxit;
   else c.status = ((den > 0.0) && isfinite(c.alpha) && isfinite(c.beta)) ? kRun : kBreakdown;
   return c;
+}
+
+// The closing check of a chunk (k_cg_advance, unpreconditioned norm): ‖r‖²
+// of the chunk's last update from k_amg_rnorm's G block partials, summed as
+// wave_partials<PU> sums the w kernel's (a lane's partials in block order,
+// then the butterfly): the bits of S[2] in the update that would follow.
+// Past G the select supplies the exact zeros that wave_partials reads from
+// its zeroed buffer — this buffer is never zeroed.  One full wave.
+__device__ __forceinline__ double cg_close_sum(const double* __restrict__ cpart, int G) {
+  const int lane = threadIdx.x & 63;
+  double a = 0.0;
+#pragma unroll
+  for (int k = 0; k < kCgMaxG / 64; ++k) {
+    const int b = lane + 64 * k;
+    a += b < G ? cpart[2 * kCgMaxG + b] : 0.0;
+  }
+  return wave_allsum(a);
+}
+// … and cg_scalars' convergence test on it.  Everything else that update
+// could find (a non-finite norm, max_it, a breakdown) is left to it: the
+// solve goes on and the update itself decides.
+__device__ __forceinline__ bool cg_close_converged(double rr, double tol2) {
+  return !(rr > tol2) && isfinite(rr);
 }
 
 // block 0 records iteration j's scalars in slots[j + 1]

@@ -66,7 +66,8 @@ struct SolveState {
   int32_t done;
   int32_t iters;
   int32_t status;  // 0 converged, -4 maxit, -5 breakdown
-  int32_t pad[2];
+  int32_t closed;  // 1: the solve ended at a chunk's closing check (k_cg_advance), not in an update
+  int32_t pad;
   double res0;     // initial value of the chosen norm² (‖b‖² or ‖M⁻¹b‖²)
   double rtol2;    // rtol², atol²: the AMG / sweep CG forms tol2 for the preconditioned
   double atol2;    // norm from its first ‖u₀‖² = ‖M⁻¹b‖² (k_amg_cg_update)
@@ -193,7 +194,11 @@ void launch_cg_iter(hipStream_t s, int j, const SellOp& op, int precond, const C
                     Slot* slots, const SolveState* st, double* part,
                     unsigned long long* trace = nullptr);
 // host: mapped pinned mirror of the final SolveState (written once, when done)
-void launch_cg_advance(hipStream_t s, int chunk, Slot* slots, SolveState* st, SolveState* host, int shift = 0);
+// cpart (non-null, shift 1, unpreconditioned norm): the chunk's closing check
+// on launch_amg_rnorm's cG block partials — convergence of the chunk's last
+// update found here, without the V-cycle and w = A u in front of the next one
+void launch_cg_advance(hipStream_t s, int chunk, Slot* slots, SolveState* st, SolveState* host, int shift = 0,
+                       const double* cpart = nullptr, int cG = 0);
 void launch_cg_init_finalize(hipStream_t s, const double* red, double rtol, double atol, int norm,
                              int max_it, double reg, SolveState* st,
                              double* zero = nullptr, int64_t nzero = 0);

@@ -20,8 +20,8 @@ def main():
         for r in csv.DictReader(f):
             rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), short(r["Kernel_Name"])))
     rows.sort()
-    # (a step on a kept K starts at its RHS-only kernel instead)
-    starts = [i for i, r in enumerate(rows) if r[2].startswith(("k_assemble", "k_amg_rhs"))]
+    # (a step on a kept K starts at its RHS-only kernel or at k_amg_start instead)
+    starts = [i for i, r in enumerate(rows) if r[2].startswith(("k_assemble", "k_amg_rhs", "k_amg_start"))]
     steps = []
     for a, b in zip(starts, starts[1:] + [len(rows)]):
         ks = rows[a:b]
