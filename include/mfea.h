@@ -226,6 +226,85 @@ int mfea_run(mfea_handle* h, int32_t n_steps, const double* dy_top, const double
              const mfea_solve_opts* opts, double max_strain, const mfea_run_records* rec,
              int32_t* n_done, int32_t* stop_reason);
 
+/* ---- event-driven failure runs (each break at its exact critical load) ------ */
+/* The reference finds failures on a ramp of fixed displacement steps
+ * (src/fea_solver.py:216-285): at each step every element over max_strain is
+ * failed in one go, so the failure loads depend on the step count, elements
+ * that would break one after another go as a batch, and the first break is
+ * reported up to one step late.  Between failures the problem is linear in the
+ * grip displacement (U ∝ dy on a fixed active set), so ONE solve at a reference
+ * load (dy_top, dy_bot) gives the load factor of the next break exactly.  One
+ * event — mfea_event — is a mfea_step at the reference load whose post is:
+ *   U₁     the solution; F₁ = Σ_top (K·U₁)_y with mfea_post's bits; ε_e the
+ *          strain of every active element, mfea_post's expression;
+ *   smax   max |ε_e| over the active elements (NaN strains — zero-length
+ *          elements — are skipped and never fail);
+ *   lam    max_strain / smax, one f64 division (+inf when smax == 0: nothing
+ *          is active or the sample has separated — the network is unloaded);
+ *   if lam <= lam_max and the network is loaded, every active element with
+ *          |ε_e| >= smax·(1 − tie_rtol) fails (product and difference rounded
+ *          once each): elements tied up to solver rounding break together.
+ *          Otherwise nothing fails: the event is terminal (n_failed == 0);
+ *   stress (E·ε_e)·lam for the elements active at event start, 0 otherwise —
+ *          the state AT the failure load; on a terminal event the factor is
+ *          lam_max when that is finite, else 1.
+ * The caller forms force = lam·force1 and displacement = lam·(dy_top − dy_bot).
+ * After an event mfea_get_displacement returns U₁ (unscaled), mfea_get_stress
+ * the event's stress row, mfea_get_active the activity after its failures.
+ * With no active element the event is the unloaded terminal one without a
+ * solve: lam = +inf, force1 = 0 (U₁ stays what the last solve left).
+ * "keep_operator" keeps nothing from one breaking event to the next — each
+ * changes the active set — but the symbolic hierarchy is kept as for steps.
+ * MFEA_EINVAL unless max_strain > 0, 0 <= tie_rtol < 1, lam_max > 0 (+inf
+ * allowed); one partition only (MFEA_ESTATE otherwise, as mfea_run). */
+typedef struct {
+  double max_strain; /* failure strain, src/fea_solver.py:20 MAX_STRAIN                      */
+  double tie_rtol;   /* relative width of the failing group below smax (1e-9 is a good default) */
+  double lam_max;    /* largest load factor of the test (+inf: none)                          */
+} mfea_event_opts;
+typedef struct {
+  double lam;       /* load factor of the event                                   */
+  double force1;    /* F₁, the reaction at the reference load                      */
+  int64_t n_failed; /* elements failed by this event (0: terminal)                */
+  int64_t n_active; /* active elements after it                                   */
+} mfea_event_out;
+int mfea_event(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opts* opts,
+               const mfea_event_opts* evopts, mfea_event_out* out, mfea_stats* st);
+
+/* n_events × mfea_event with the same internals, each followed by its record
+ * rows, gathered and copied out as mfea_run's are (its two device slabs, copy
+ * stream and page-locking, with the pinned fallback): U row k = lam_k·U₁ (one
+ * multiply per entry, on the device), stress row k, activity after event k.
+ *   - a solver failure at event k ends the run: returns 0, *stop_reason = that
+ *     code, *n_done = k, row k is not written;
+ *   - a terminal event k is recorded in full (n_failed[k] == 0): *n_done = k + 1
+ *     and *stop_reason = MFEA_EVENTS_LAMBDA_MAX (lam_k > lam_max) or
+ *     MFEA_EVENTS_UNLOADED (smax == 0);
+ *   - otherwise MFEA_EVENTS_COMPLETE after n_events events.
+ * Rows >= *n_done are untouched.  event_of[e] = the event (counted from this
+ * call's start) that failed element e, -1 if it is still active or was
+ * inactive at the call's start. */
+typedef struct {
+  double* U;         /* n_events × 3·n_nodes; NULL = not kept */
+  double* stress;    /* n_events × n_elems; NULL = not kept    */
+  uint8_t* active;   /* n_events × n_elems; NULL = not kept    */
+  double* lam;       /* n_events (required)                    */
+  double* force1;    /* n_events (required)                    */
+  int64_t* n_failed; /* n_events (required)                    */
+  int64_t* n_active; /* n_events (required)                    */
+  int32_t* event_of; /* n_elems, or NULL                       */
+  mfea_stats* stats; /* n_events, or NULL                      */
+  double* wall_s;    /* n_events, or NULL: host wall time of event k */
+} mfea_event_records;
+
+#define MFEA_EVENTS_COMPLETE 0   /* all n_events ran, each with failures       */
+#define MFEA_EVENTS_LAMBDA_MAX 1 /* event n_done - 1 needs lam > lam_max        */
+#define MFEA_EVENTS_UNLOADED 2   /* event n_done - 1 found no strain (smax == 0) */
+
+int mfea_run_events(mfea_handle* h, int32_t n_events, double dy_top, double dy_bot,
+                    const mfea_solve_opts* opts, const mfea_event_opts* evopts,
+                    const mfea_event_records* rec, int32_t* n_done, int32_t* stop_reason);
+
 /* ---- reference-API helpers ------------------------------------------------- */
 /* bar_stiffness_bulk on device (src/fea_solver.py:30-68): Ke n×36 row-major, L n. */
 int mfea_element_stiffness(mfea_handle* h, int64_t n, const double* p1s, const double* p2s,

@@ -109,6 +109,10 @@ int mfea_debug_floating(mfea_handle* h, uint8_t* out);
  *                        each row straight into them (1); 0: through two pinned host slabs
  *                        and a host memcpy (the path taken when page-locking fails).
  *                        Read-only "run_direct": which of the two the last mfea_run took
+ *   "event_scratch" 0|1  mfea_event / mfea_run_events: the event scan keeps every element's
+ *                        strain in a scratch array of n_elems doubles for the apply kernel
+ *                        (1); 0: the apply forms the strains again from U₁ (same bits) —
+ *                        DESIGN.md §4.9
  *   "keep_operator" 0|1  mfea_step, one partition: keep K while the active set, the material,
  *                        the build and asm_kernel hold (only the RHS is formed), and keep the
  *                        GAMG hierarchy's values while K, the plan, the floating mask, reg

@@ -110,6 +110,8 @@ struct Part {
   DevBuf<int32_t> slice_ptr, row_len, s_col, s_elem, e2n_d;
   DevBuf<uint8_t> active, code, elem_own;
   DevBuf<int32_t> fail_list;  // (owned) elements failed in the last post (any order)
+  DevBuf<int32_t> event_of;   // mfea_event / mfea_run_events: the event that failed each element (-1: none)
+  DevBuf<double> eps;         // the event scan's strains, for k_event_apply (option "event_scratch")
   DevBuf<int32_t> amg_inv;    // Pattern row → level-0 row (k_amg_start), for the plan below
   int64_t amg_inv_gen = -1;
   const int32_t* amg_inv_row0 = nullptr;
@@ -356,6 +358,15 @@ struct mfea_handle {
   bool spec_used = false;  // one speculative post per step: behind the planned batch only
   bool spec_launched = false;
   double spec_strain = 0.0;
+  // mfea_event / mfea_run_events: the post of this step is the event pair
+  // (k_event_scan, k_event_apply; events.hip) with these parameters.  It rides
+  // where the post rides behind an eagerly launched batch (spec_post, undone
+  // by k_event_unfail); the batch graph holds the plain post only, so an event
+  // step does not take it.
+  bool ev_on = false;
+  double ev_strain = 0.0, ev_tie = 0.0, ev_lam_max = 0.0;
+  int32_t ev_index = 0;
+  int opt_event_scratch = 1;  // option "event_scratch": 1 the scan keeps ε_e for the apply, 0 it forms them again
   hipEvent_t poll[2] = {};
   int64_t n_active = 0;
   bool act_all = false;  // every element is active on the device (set_active(NULL), no failure since)
@@ -748,6 +759,11 @@ int upload_part(mfea_handle* h, Part& pt, bool dm) {
   }
   HIPC(pt.fail_list.alloc(std::max<int64_t>(E, 1)));
   HIPC(pt.fail_cnt.alloc(1));
+  if (!dm) {
+    HIPC(pt.event_of.alloc(std::max<int64_t>(E, 1)));
+    HIPC(pt.eps.alloc(std::max<int64_t>(E, 1)));
+    HIPC(hipMemsetAsync(pt.event_of.ptr, 0xFF, std::max<int64_t>(E, 1) * sizeof(int32_t), s));
+  }
   HIPC(hipStreamSynchronize(s));
   return 0;
 }
@@ -2430,7 +2446,7 @@ int solve_amg(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opt
   // mfea_step: the planned batch, the finish and the post as ONE graph of the
   // batch's exact length (option batch_graph), behind the setup in the same
   // graph (option combo_graph)
-  const bool batch = h->spec_on && !h->spec_used && h->opt_batch_graph && !h->opt_phase_times &&
+  const bool batch = h->spec_on && !h->ev_on && !h->spec_used && h->opt_batch_graph && !h->opt_phase_times &&
                      o->chunk <= 0 && need < mfea_handle::kRemGraphs && h->opt_graph;
   const bool combo = batch && entry && h->opt_combo_graph;
   // (combo: the graph reaches the batch's end and publishes the state; the
@@ -3476,7 +3492,9 @@ int enqueue_post(mfea_handle* h, double max_strain) {
 }
 // the post's kernels and the read-back of their sums into the pinned h_red
 // (capturable: the batch graph holds them)
+int enqueue_event_work(mfea_handle* h);
 int enqueue_post_work(mfea_handle* h, double max_strain) {
+  if (h->ev_on) return enqueue_event_work(h);
   hipStream_t s = h->stream;
   const bool dm = partitioned(h);
   for (auto& pp : h->parts) {
@@ -3505,6 +3523,68 @@ int enqueue_post_work(mfea_handle* h, double max_strain) {
   return 0;
 }
 
+// The post of an event (mfea_event; one partition): the scan — reaction and
+// strains, one launch — then the apply, which reads the scan's maximum from
+// device memory; then the read-back of F₁, #active, the failure counter, smax
+// and lam (red[4..8]) into h_red[0..4].  Same tickets, failed-element list and
+// counter as the plain post, so post_impl's bookkeeping serves both.
+int enqueue_event_work(mfea_handle* h) {
+  hipStream_t s = h->stream;
+  Part& pt = part0(h);
+  const Pattern& P = pt.P;
+  if ((int64_t)pt.partials.n < event_scan_partials(P.n_top, P.n_elems))
+    return fail(MFEA_EINVAL, "internal: partials too small for the event scan");
+  double* eps = h->opt_event_scratch ? pt.eps.ptr : nullptr;
+  EventScan q{};
+  q.row0 = P.n_free;
+  q.nrows = P.n_top;
+  q.N = P.n_nodes;
+  q.slice_ptr = pt.slice_ptr.ptr;
+  q.row_len = pt.row_len.ptr;
+  q.s_col = pt.s_col.ptr;
+  q.val = pt.val.ptr;
+  q.diag = pt.diag.ptr;
+  q.G = pt.G;
+  q.u = pt.x.ptr;
+  q.partials = pt.partials.ptr;
+  q.ticket_r = tix(pt, 3);
+  q.force_out = pt.red.ptr + 4;
+  q.E = P.n_elems;
+  q.e2n = pt.e2n_d.ptr;
+  q.xyz = pt.xyz_d.ptr;
+  q.active = pt.active.ptr;
+  q.eps = eps;
+  q.ticket_e = tix(pt, 4);
+  q.cnt_out = pt.red.ptr + 5;
+  q.smax_out = pt.red.ptr + 7;
+  launch_event_scan(s, q);
+  EventApply a{};
+  a.E = P.n_elems;
+  a.e2n = pt.e2n_d.ptr;
+  a.xyz = pt.xyz_d.ptr;
+  a.u = pt.x.ptr;
+  a.eps = eps;
+  a.Emod = h->mat.E;
+  a.max_strain = h->ev_strain;
+  a.tie_rtol = h->ev_tie;
+  a.lam_max = h->ev_lam_max;
+  a.k = h->ev_index;
+  a.smax = pt.red.ptr + 7;
+  a.active = pt.active.ptr;
+  a.stress = pt.stress.ptr;
+  a.event_of = pt.event_of.ptr;
+  a.fail_list = pt.fail_list.ptr;
+  a.fail_cnt = fail_counter(pt);
+  a.partials = pt.partials.ptr;
+  a.ticket = tix(pt, 4);
+  a.cnt_out = pt.red.ptr + 5;
+  a.lam_out = pt.red.ptr + 8;
+  launch_event_apply(s, a);
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpyAsync(h->h_red, pt.red.ptr + 4, 5 * sizeof(double), hipMemcpyDeviceToHost, s));
+  return 0;
+}
+
 // Speculative post (mfea_handle::spec_on), enqueued behind the solve's
 // planned batch: the solve's end event, then the post.  At any later batch
 // end the solve went on: that post's failures are undone and post runs after
@@ -3524,7 +3604,8 @@ int spec_post(mfea_handle* h) {
 int spec_undo(mfea_handle* h) {
   if (!h->spec_launched) return 0;
   Part& pt = part0(h);
-  launch_unfail(h->stream, pt.fail_list.ptr, fail_counter(pt), pt.active.ptr);
+  if (h->ev_on) launch_event_unfail(h->stream, pt.fail_list.ptr, fail_counter(pt), pt.active.ptr, pt.event_of.ptr);
+  else launch_unfail(h->stream, pt.fail_list.ptr, fail_counter(pt), pt.active.ptr);
   HIPC(hipGetLastError());
   h->spec_launched = false;
   return 0;
@@ -3866,11 +3947,9 @@ int mfea_post(mfea_handle* h, double max_strain, double* total_force, int64_t* n
   return post_impl(h, max_strain, total_force, n_active, nullptr);
 }
 
-int mfea_step(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opts* opts,
-              double max_strain, double* total_force, int64_t* n_active, mfea_stats* st) {
-  if (!h) return fail(MFEA_EINVAL, "NULL handle");
-  RC(set_device(h));
-  RC(ensure_built(h));
+// mfea_step's body; h->ev_on: the post is the event pair (mfea_event)
+static int step_impl(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opts* opts,
+                     double max_strain, double* total_force, int64_t* n_active, mfea_stats* st) {
   mfea_solve_opts o = opts ? *opts : default_opts();
   if (st) std::memset(st, 0, sizeof(*st));
   // the one-partition GAMG / SOR / ICC solves take their RHS from the
@@ -3942,6 +4021,71 @@ int mfea_step(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opt
     solve_times(h, st);
   }
   return 0;
+}
+
+int mfea_step(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opts* opts,
+              double max_strain, double* total_force, int64_t* n_active, mfea_stats* st) {
+  if (!h) return fail(MFEA_EINVAL, "NULL handle");
+  RC(set_device(h));
+  RC(ensure_built(h));
+  return step_impl(h, dy_top, dy_bot, opts, max_strain, total_force, n_active, st);
+}
+
+// ---------------------------------------------------------------------------
+// mfea_event: one step at the reference load whose post is the event pair.
+// ---------------------------------------------------------------------------
+static int event_check(const mfea_event_opts* ev) {
+  if (!ev) return fail(MFEA_EINVAL, "NULL argument");
+  if (!(ev->max_strain > 0.0)) return fail(MFEA_EINVAL, "mfea_event: max_strain must be > 0");
+  if (!(ev->tie_rtol >= 0.0 && ev->tie_rtol < 1.0)) return fail(MFEA_EINVAL, "mfea_event: tie_rtol must be in [0, 1)");
+  if (!(ev->lam_max > 0.0)) return fail(MFEA_EINVAL, "mfea_event: lam_max must be > 0 (+inf allowed)");
+  return 0;
+}
+
+// event `index` of a run (0 for a single mfea_event) on a built one-partition handle
+static int event_impl(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opts* opts,
+                      const mfea_event_opts* ev, int32_t index, mfea_event_out* out, mfea_stats* st) {
+  h->ev_strain = ev->max_strain;
+  h->ev_tie = ev->tie_rtol;
+  h->ev_lam_max = ev->lam_max;
+  h->ev_index = index;
+  double f1 = 0.0;
+  int64_t na = 0;
+  h->ev_on = true;
+  int rc;
+  if (h->n_active == 0) {
+    // nothing is active: the unloaded terminal event without a solve
+    // (lam = +inf from the scan, F₁ = 0; U₁ stays what the last solve left)
+    if (st) std::memset(st, 0, sizeof(*st));
+    h->spec_launched = false;
+    rc = post_impl(h, ev->max_strain, &f1, &na, nullptr);
+    if (rc) {
+      drop_kept(h);
+      (void)sync_stream(h);
+    }
+    f1 = 0.0;
+  } else {
+    rc = step_impl(h, dy_top, dy_bot, opts, ev->max_strain, &f1, &na, st);
+  }
+  h->ev_on = false;
+  if (rc) return rc;
+  unsigned nfail = 0;
+  std::memcpy(&nfail, &h->h_red[2], sizeof nfail);
+  out->lam = h->h_red[4];
+  out->force1 = f1;
+  out->n_failed = (int64_t)nfail;
+  out->n_active = na;
+  return 0;
+}
+
+int mfea_event(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opts* opts,
+               const mfea_event_opts* evopts, mfea_event_out* out, mfea_stats* st) {
+  RC(event_check(evopts));  // (first: the options are checked whatever the handle)
+  if (!h || !out) return fail(MFEA_EINVAL, "NULL argument");
+  RC(set_device(h));
+  RC(ensure_built(h));
+  if (partitioned(h)) return fail(MFEA_ESTATE, "mfea_event: one partition per handle");
+  return event_impl(h, dy_top, dy_bot, opts, evopts, 0, out, st);
 }
 
 int mfea_get_displacement(mfea_handle* h, double* U) {
@@ -4081,10 +4225,89 @@ int run_drain(mfea_handle* h, RunCtx& c) {
   return 0;
 }
 
+// row k: the gather into slab k&1 on the handle's stream and its copy out on
+// the copy stream.  lam (device memory): the rows of an event, U scaled by it
+// (mfea_run_events); NULL: a step's rows
+int run_emit(mfea_handle* h, Part& pt, RunCtx& c, int32_t k, const double* lam) {
+  const int64_t N = pt.P.n_nodes, E = pt.P.n_elems;
+  const int s = k & 1;
+  uint8_t* slab = pt.rec_slab[s].ptr;
+  double* u_row = c.dst[0] ? reinterpret_cast<double*>(slab + c.off[0]) : nullptr;
+  double* s_row = c.dst[1] ? reinterpret_cast<double*>(slab + c.off[1]) : nullptr;
+  uint8_t* a_row = c.dst[2] ? slab + c.off[2] : nullptr;
+  // slab s was last read by the copies of step k - 2
+  if (k >= 2) HIPC(hipStreamWaitEvent(h->stream, h->run_free[s], 0));
+  if (lam)
+    launch_record_event(h->stream, N, pt.iperm_d.ptr, pt.x.ptr, lam, u_row, E, pt.stress.ptr, s_row, pt.active.ptr,
+                        a_row);
+  else
+    launch_record_step(h->stream, N, pt.iperm_d.ptr, pt.x.ptr, u_row, E, pt.stress.ptr, s_row, pt.active.ptr,
+                       a_row);
+  HIPC(hipGetLastError());
+  HIPC(hipEventRecord(h->run_ready[s], h->stream));
+  HIPC(hipStreamWaitEvent(h->run_copy, h->run_ready[s], 0));
+  for (int j = 0; j < 3; ++j) {
+    if (!c.dst[j] || !c.row_b[j]) continue;
+    uint8_t* to = c.direct ? c.dst[j] + (size_t)k * c.row_b[j] : h->run_pin[s] + c.off[j];
+    HIPC(hipMemcpyAsync(to, slab + c.off[j], c.row_b[j], hipMemcpyDeviceToHost, h->run_copy));
+  }
+  HIPC(hipEventRecord(h->run_free[s], h->run_copy));
+  if (!c.direct) {
+    // row k - 1 was copied out while step k ran: move it now, while row k's
+    // copy runs, before step k + 1's copy reuses its pinned slab
+    RC(run_drain(h, c));
+    c.pending = k;
+  }
+  return 0;
+}
+
+// the record arrays of a run of n_rows rows: slab layout, staging, page-locking
+// (or the pinned slabs where that fails)
+int run_open(mfea_handle* h, Part& pt, RunCtx& c, RunRegistered& reg, int32_t n_rows, double* U, double* stress,
+             uint8_t* active) {
+  c.L = record_slab(pt.P.n_nodes, pt.P.n_elems);
+  RC(run_prepare(h, pt, c.L));
+  c.dst[0] = reinterpret_cast<uint8_t*>(U);
+  c.dst[1] = reinterpret_cast<uint8_t*>(stress);
+  c.dst[2] = active;
+  c.row_b[0] = (size_t)pt.P.n_nodes * 24;
+  c.row_b[1] = (size_t)pt.P.n_elems * 8;
+  c.row_b[2] = (size_t)pt.P.n_elems;
+  c.off[0] = c.L.off_u;
+  c.off[1] = c.L.off_s;
+  c.off[2] = c.L.off_a;
+  c.direct = h->opt_run_register;
+  for (int j = 0; j < 3 && c.direct; ++j) {
+    if (!c.dst[j] || !c.row_b[j]) continue;
+    if (hipHostRegister(c.dst[j], (size_t)n_rows * c.row_b[j], hipHostRegisterDefault) == hipSuccess) {
+      reg.ptr[reg.n++] = c.dst[j];
+    } else {
+      (void)hipGetLastError();
+      c.direct = false;
+    }
+  }
+  if (!c.direct) {
+    reg.release();
+    RC(run_pinned(h, (size_t)c.L.bytes));
+  }
+  h->run_direct = c.direct ? 1 : 0;
+  return 0;
+}
+
+// every exit of a run: the copies issued so far land before the arrays are released
+int run_close(mfea_handle* h, RunCtx& c, RunRegistered& reg, int rc, const char* who) {
+  const int rd = run_drain(h, c);
+  const hipError_t es = hipStreamSynchronize(h->run_copy);
+  reg.release();
+  if (rc == 0) rc = rd;
+  if (rc == 0 && es != hipSuccess)
+    rc = fail(MFEA_EDEVICE, std::string(who) + ": copy stream: " + hipGetErrorString(es));
+  return rc;
+}
+
 int run_steps(mfea_handle* h, Part& pt, RunCtx& c, int32_t n_steps, const double* dy_top, const double* dy_bot,
               const mfea_solve_opts* opts, double max_strain, const mfea_run_records* rec, int32_t* n_done,
               int32_t* stop_reason) {
-  const int64_t N = pt.P.n_nodes, E = pt.P.n_elems;
   for (int32_t k = 0; k < n_steps; ++k) {
     double force = 0.0;
     int64_t na = 0;
@@ -4101,29 +4324,7 @@ int run_steps(mfea_handle* h, Part& pt, RunCtx& c, int32_t n_steps, const double
     rec->n_active[k] = na;
     if (rec->stats) rec->stats[k] = st;
     if (rec->wall_s) rec->wall_s[k] = wall;
-    const int s = k & 1;
-    uint8_t* slab = pt.rec_slab[s].ptr;
-    // slab s was last read by the copies of step k - 2
-    if (k >= 2) HIPC(hipStreamWaitEvent(h->stream, h->run_free[s], 0));
-    launch_record_step(h->stream, N, pt.iperm_d.ptr, pt.x.ptr,
-                       c.dst[0] ? reinterpret_cast<double*>(slab + c.off[0]) : nullptr, E, pt.stress.ptr,
-                       c.dst[1] ? reinterpret_cast<double*>(slab + c.off[1]) : nullptr, pt.active.ptr,
-                       c.dst[2] ? slab + c.off[2] : nullptr);
-    HIPC(hipGetLastError());
-    HIPC(hipEventRecord(h->run_ready[s], h->stream));
-    HIPC(hipStreamWaitEvent(h->run_copy, h->run_ready[s], 0));
-    for (int j = 0; j < 3; ++j) {
-      if (!c.dst[j] || !c.row_b[j]) continue;
-      uint8_t* to = c.direct ? c.dst[j] + (size_t)k * c.row_b[j] : h->run_pin[s] + c.off[j];
-      HIPC(hipMemcpyAsync(to, slab + c.off[j], c.row_b[j], hipMemcpyDeviceToHost, h->run_copy));
-    }
-    HIPC(hipEventRecord(h->run_free[s], h->run_copy));
-    if (!c.direct) {
-      // row k - 1 was copied out while step k ran: move it now, while row k's
-      // copy runs, before step k + 1's copy reuses its pinned slab
-      RC(run_drain(h, c));
-      c.pending = k;
-    }
+    RC(run_emit(h, pt, c, k, nullptr));
     *n_done = k + 1;
     if (na == 0) {
       *stop_reason = MFEA_RUN_NO_ACTIVE;
@@ -4152,41 +4353,65 @@ int mfea_run(mfea_handle* h, int32_t n_steps, const double* dy_top, const double
   if (n_steps == 0) return 0;
   Part& pt = part0(h);
   RunCtx c;
-  c.L = record_slab(pt.P.n_nodes, pt.P.n_elems);
-  RC(run_prepare(h, pt, c.L));
-  c.dst[0] = reinterpret_cast<uint8_t*>(rec->U);
-  c.dst[1] = reinterpret_cast<uint8_t*>(rec->stress);
-  c.dst[2] = rec->active;
-  c.row_b[0] = (size_t)pt.P.n_nodes * 24;
-  c.row_b[1] = (size_t)pt.P.n_elems * 8;
-  c.row_b[2] = (size_t)pt.P.n_elems;
-  c.off[0] = c.L.off_u;
-  c.off[1] = c.L.off_s;
-  c.off[2] = c.L.off_a;
   RunRegistered reg;
-  c.direct = h->opt_run_register;
-  for (int j = 0; j < 3 && c.direct; ++j) {
-    if (!c.dst[j] || !c.row_b[j]) continue;
-    if (hipHostRegister(c.dst[j], (size_t)n_steps * c.row_b[j], hipHostRegisterDefault) == hipSuccess) {
-      reg.ptr[reg.n++] = c.dst[j];
-    } else {
-      (void)hipGetLastError();
-      c.direct = false;
+  RC(run_open(h, pt, c, reg, n_steps, rec->U, rec->stress, rec->active));
+  const int rc = run_steps(h, pt, c, n_steps, dy_top, dy_bot, opts, max_strain, rec, n_done, stop_reason);
+  return run_close(h, c, reg, rc, "mfea_run");
+}
+
+// The event loop of mfea_run_events: n_events × mfea_event, each followed by
+// its record rows (the U row scaled by the event's lam on the device).
+int mfea_run_events(mfea_handle* h, int32_t n_events, double dy_top, double dy_bot, const mfea_solve_opts* opts,
+                    const mfea_event_opts* evopts, const mfea_event_records* rec, int32_t* n_done,
+                    int32_t* stop_reason) {
+  RC(event_check(evopts));
+  if (!h || !rec || !n_done || !stop_reason) return fail(MFEA_EINVAL, "NULL argument");
+  if (n_events < 0) return fail(MFEA_EINVAL, "negative n_events");
+  if (n_events && (!rec->lam || !rec->force1 || !rec->n_failed || !rec->n_active))
+    return fail(MFEA_EINVAL, "mfea_run_events: lam, force1, n_failed and n_active are required");
+  *n_done = 0;
+  *stop_reason = MFEA_EVENTS_COMPLETE;
+  RC(set_device(h));
+  RC(ensure_built(h));
+  if (partitioned(h)) return fail(MFEA_ESTATE, "mfea_run_events: one partition per handle");
+  Part& pt = part0(h);
+  const int64_t E = pt.P.n_elems;
+  if (E) HIPC(hipMemsetAsync(pt.event_of.ptr, 0xFF, E * sizeof(int32_t), h->stream));
+  int rc = 0;
+  if (n_events > 0) {
+    RunCtx c;
+    RunRegistered reg;
+    RC(run_open(h, pt, c, reg, n_events, rec->U, rec->stress, rec->active));
+    for (int32_t k = 0; k < n_events && rc == 0; ++k) {
+      mfea_event_out out;
+      mfea_stats st;
+      const auto t0 = std::chrono::steady_clock::now();
+      rc = event_impl(h, dy_top, dy_bot, opts, evopts, k, &out, &st);
+      const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      if (rc == MFEA_EMAXIT || rc == MFEA_EBREAKDOWN) {
+        *stop_reason = rc;
+        rc = 0;
+        break;
+      }
+      if (rc) break;
+      rec->lam[k] = out.lam;
+      rec->force1[k] = out.force1;
+      rec->n_failed[k] = out.n_failed;
+      rec->n_active[k] = out.n_active;
+      if (rec->stats) rec->stats[k] = st;
+      if (rec->wall_s) rec->wall_s[k] = wall;
+      rc = run_emit(h, pt, c, k, pt.red.ptr + 8);
+      if (rc) break;
+      *n_done = k + 1;
+      if (out.n_failed == 0) {  // terminal: smax = 0 (unloaded) or lam > lam_max
+        *stop_reason = h->h_red[3] > 0.0 ? MFEA_EVENTS_LAMBDA_MAX : MFEA_EVENTS_UNLOADED;
+        break;
+      }
     }
+    rc = run_close(h, c, reg, rc, "mfea_run_events");
   }
-  if (!c.direct) {
-    reg.release();
-    RC(run_pinned(h, (size_t)c.L.bytes));
-  }
-  h->run_direct = c.direct ? 1 : 0;
-  int rc = run_steps(h, pt, c, n_steps, dy_top, dy_bot, opts, max_strain, rec, n_done, stop_reason);
-  // every exit: the copies issued so far land before the arrays are released
-  const int rd = run_drain(h, c);
-  const hipError_t es = hipStreamSynchronize(h->run_copy);
-  reg.release();
-  if (rc == 0) rc = rd;
-  if (rc == 0 && es != hipSuccess)
-    rc = fail(MFEA_EDEVICE, std::string("mfea_run: copy stream: ") + hipGetErrorString(es));
+  if (rc == 0 && rec->event_of && E)
+    HIPC(hmemcpy(h, rec->event_of, pt.event_of.ptr, E * sizeof(int32_t), hipMemcpyDeviceToHost));
   return rc;
 }
 
@@ -4553,6 +4778,7 @@ int mfea_set_option(mfea_handle* h, const char* name, int64_t value) {
   bool rebuild = false;  // options baked into the symbolic layout
   if (n == "graph") h->opt_graph = value != 0;
   else if (n == "run_register") h->opt_run_register = value != 0;
+  else if (n == "event_scratch") h->opt_event_scratch = value != 0;
   else if (n == "phase_times") h->opt_phase_times = value != 0;
   else if (n == "dist_graph") h->opt_dist_graph = value != 0;
   else if (n == "order") { h->opt_order = (int)value; rebuild = true; }
@@ -4903,6 +5129,7 @@ int mfea_get_option(mfea_handle* h, const char* name, int64_t* value) {
     if (n == pn && h->parts.empty()) return fail(MFEA_ESTATE, std::string(name) + ": no partition yet");
   if (n == "graph") *value = h->opt_graph;
   else if (n == "run_register") *value = h->opt_run_register ? 1 : 0;
+  else if (n == "event_scratch") *value = h->opt_event_scratch;
   else if (n == "run_direct") *value = h->run_direct;  // read-only: the last mfea_run's host path
   else if (n == "phase_times") *value = h->opt_phase_times ? 1 : 0;
   else if (n == "dist_graph") *value = h->opt_dist_graph;

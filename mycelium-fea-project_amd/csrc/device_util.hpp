@@ -91,13 +91,15 @@ __device__ __forceinline__ double load_sc1(const double* p) {
 // release/acquire fence on the per-iteration path.
 // partials must hold NV·(gridDim + kShards) doubles.
 // ---------------------------------------------------------------------------
+// block_publish_as: the same over blocks b = 0..G-1 of a launch that holds
+// other blocks too (k_event_scan's two row sets: each set reduces as its own
+// kernel would, with its own partials and ticket set).
 template <int NV, int BS = kBlock>
-__device__ __forceinline__ bool block_publish(double (&v)[NV], double* partials,
-                                              unsigned* ticket, double* out) {
+__device__ __forceinline__ bool block_publish_as(double (&v)[NV], double* partials, unsigned* ticket,
+                                                 double* out, const unsigned G, const unsigned b) {
   constexpr int NW = BS / 64;
   __shared__ double lds[NW * NV];
   __shared__ int flag;
-  const unsigned G = gridDim.x, b = blockIdx.x;
   const unsigned S = G < (unsigned)kShards ? G : (unsigned)kShards;
   const unsigned shard = b % S;
   const unsigned nshard = (G - shard + S - 1) / S;
@@ -160,6 +162,12 @@ __device__ __forceinline__ bool block_publish(double (&v)[NV], double* partials,
     __hip_atomic_store(&ticket[kShards * 16], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   return true;
+}
+
+template <int NV, int BS = kBlock>
+__device__ __forceinline__ bool block_publish(double (&v)[NV], double* partials,
+                                              unsigned* ticket, double* out) {
+  return block_publish_as<NV, BS>(v, partials, ticket, out, gridDim.x, blockIdx.x);
 }
 
 __device__ __forceinline__ void sym_apply(const double B[6], const double v[3], double o[3]) {

@@ -152,6 +152,61 @@ void launch_stress(hipStream_t s, int64_t E, const int32_t* e2n, const double* x
                    double* stress, double* partials, unsigned* ticket, double* red_out,
                    const uint8_t* owned = nullptr, int32_t* fail_list = nullptr, unsigned* fail_cnt = nullptr);
 
+// ---- event-driven failure runs (events.hip) ---------------------------------
+// k_event_scan: the reaction of the top grip rows (launch_reaction's arguments;
+// force_out gets k_reaction's bits) and, in the same launch, the elements'
+// strains: cnt_out = #active, smax_out = max |ε| over the active elements (NaN
+// skipped), eps (E doubles, or NULL) = every ε_e.  partials holds at least
+// event_scan_partials(nrows, E) doubles; the launcher sets the grid_* /
+// partials_* / pmax fields.
+struct EventScan {
+  int64_t row0, nrows, N;
+  const int32_t *slice_ptr, *row_len, *s_col;
+  const double *val, *diag;
+  int64_t G;
+  const double* u;
+  double* partials;
+  unsigned* ticket_r;
+  double* force_out;
+  int64_t E;
+  const int32_t* e2n;
+  const double* xyz;
+  const uint8_t* active;
+  double* eps;
+  unsigned* ticket_e;
+  double *cnt_out, *smax_out;
+  unsigned grid_r, grid_e;
+  double *partials_r, *partials_e, *pmax;
+};
+void launch_event_scan(hipStream_t s, EventScan q);
+int64_t event_scan_partials(int64_t n_top, int64_t n_elems);
+// k_event_apply: lam = max_strain / *smax, the failing group (activity cleared,
+// event_of = k, appended to fail_list as launch_stress appends), the stress row
+// at the failure load, cnt_out = #active after, lam_out = lam.  eps: the scan's
+// strains, or NULL to form them again from u.
+struct EventApply {
+  int64_t E;
+  const int32_t* e2n;
+  const double* xyz;
+  const double* u;
+  const double* eps;
+  double Emod, max_strain, tie_rtol, lam_max;
+  int32_t k;
+  const double* smax;
+  uint8_t* active;
+  double* stress;
+  int32_t* event_of;
+  int32_t* fail_list;
+  unsigned* fail_cnt;
+  double* partials;
+  unsigned* ticket;
+  double *cnt_out, *lam_out;
+};
+void launch_event_apply(hipStream_t s, const EventApply& q);
+// k_event_apply's failures undone: active again, event_of = -1, counter zero
+void launch_event_unfail(hipStream_t s, const int32_t* fail_list, unsigned* cnt, uint8_t* active,
+                         int32_t* event_of);
+
 void launch_element_stiffness(hipStream_t s, int64_t n, const double* p1, const double* p2,
                               Material m, double* Ke, double* L);
 

@@ -31,4 +31,10 @@ void launch_record_step(hipStream_t s, int64_t N, const int32_t* iperm, const do
                         int64_t E, const double* stress, double* s_row, const uint8_t* active,
                         uint8_t* a_row);
 
+// The rows of an event (mfea_run_events): as launch_record_step, with
+// u_row[3g + a] = *lam · x[3·iperm[g] + a] (lam: device memory).
+void launch_record_event(hipStream_t s, int64_t N, const int32_t* iperm, const double* x, const double* lam,
+                         double* u_row, int64_t E, const double* stress, double* s_row,
+                         const uint8_t* active, uint8_t* a_row);
+
 }  // namespace mfea

@@ -173,7 +173,8 @@ def _grips(nodes, coords, tol):
 
 
 def fea_solver(results_dir, tol=GRIP_LENGTH, *, rtol=None, max_it=None, precond=None,
-               out_format="python", verbose=True, nparts=1, npy=False, device_run=False):
+               out_format="python", verbose=True, nparts=1, npy=False, device_run=False,
+               events=False, tie_rtol=1e-9, max_events=None):
     """The reference step loop (src/fea_solver.py:186-335) with the hot path on device.
 
     Reads <results_dir>/nodes.csv + elements.csv, runs N_STEPS load steps and
@@ -194,9 +195,22 @@ def fea_solver(results_dir, tol=GRIP_LENGTH, *, rtol=None, max_it=None, precond=
     device_run=True (one process, one partition) runs the step loop as ONE
     library call (Engine.run / mfea_run): every step's records are gathered on
     the device and copied out while the next step computes.  Same files, same
-    returned dict; the per-step progress lines are printed after the run."""
+    returned dict; the per-step progress lines are printed after the run.
+
+    events=True (one process, one partition) replaces the fixed ramp by the
+    event-driven run (Engine.run_events / mfea_run_events): one solve at the
+    reference load ±DISPLACEMENT_MAX per failure event, each break at its exact
+    load factor lam (lam_max = 1: the test's full travel), elements within
+    tie_rtol of the largest strain breaking together, at most max_events
+    events (default n_elems + 1).  The four records hold one row per event —
+    the state at the failure load; force_displacement.csv holds (lam·span,
+    lam·F₁) — and failure_events.csv lists event, lam, total_displacement,
+    total_force, n_failed, n_active.  npy=True also writes event_of.npy (the
+    event that failed each element, -1 = none)."""
     start_time = time.time()
     rank, world = dist_env()
+    if events and (world > 1 or nparts > 1):
+        raise ValueError("events needs one process and one partition (world == 1, nparts == 1)")
     if device_run and (world > 1 or nparts > 1):
         raise ValueError("device_run needs one process and one partition (world == 1, nparts == 1)")
     say = print if verbose and rank == 0 else (lambda *a, **k: None)
@@ -233,9 +247,12 @@ def fea_solver(results_dir, tol=GRIP_LENGTH, *, rtol=None, max_it=None, precond=
     if rank == 0:
         with open(os.path.join(fea_dir, "solve_runtime.txt"), "w") as f:
             f.write("step, runtime_s\n")
-    if device_run:
+    if events:
+        stress_record, active_record, disp_record, force_disp_curve = _event_run(
+            eng, opts, fea_dir, say, tie_rtol, max_events, npy)
+    elif device_run:
         stress_record, active_record, disp_record, force_disp_curve = _device_run(eng, opts, fea_dir, say)
-    for step in range(0 if device_run else N_STEPS):  # the per-step path
+    for step in range(0 if device_run or events else N_STEPS):  # the per-step path
         disp_factor = step / (N_STEPS - 1)
         dy_top = +DISPLACEMENT_MAX * disp_factor
         dy_bot = -DISPLACEMENT_MAX * disp_factor
@@ -300,6 +317,41 @@ def _device_run(eng, opts, fea_dir, say):
     return run["stress"], run["active"], run["U"], force_disp_curve
 
 
+def _event_run(eng, opts, fea_dir, say, tie_rtol, max_events, npy):
+    """The event-driven failure run of fea_solver(events=True): one library
+    call (Engine.run_events / mfea_run_events) at the reference load
+    ±DISPLACEMENT_MAX with lam_max = 1.  Writes failure_events.csv (and
+    event_of.npy with npy) and solve_runtime.txt; returns the four records, one
+    row per event."""
+    span = DISPLACEMENT_MAX - (-DISPLACEMENT_MAX)
+    run = eng.run_events(+DISPLACEMENT_MAX, -DISPLACEMENT_MAX, opts, MAX_STRAIN, tie_rtol=tie_rtol, lam_max=1.0,
+                         n_events=max_events)
+    n_done = run["n_done"]
+    with open(os.path.join(fea_dir, "solve_runtime.txt"), "a") as f:
+        for k in range(n_done):
+            say(f"➡️  Event {k+1} | lam={run['lam'][k]:.6g}, failed={run['n_failed'][k]}, "
+                f"active={run['n_active'][k]}")
+            f.write(f"{k+1}, {run['wall_s'][k]:.6f}\n")
+    stop = run["stop_reason"]
+    if stop in (_capi.EMAXIT, _capi.EBREAKDOWN):
+        say(f"❌ Singular matrix at event {n_done+1}. Saving partial results and stopping.")
+    elif stop == _capi.EVENTS_LAMBDA_MAX:
+        say(f"✅ No further failure within the test's travel (event {n_done}).")
+    elif stop == _capi.EVENTS_UNLOADED:
+        say(f"⚠️  The network carries no load at event {n_done}.")
+    curve = [[float(run["lam"][k] * span), float(run["lam"][k] * run["force1"][k])] for k in range(n_done)]
+    with open(os.path.join(fea_dir, "failure_events.csv"), "w") as f:
+        f.write("event,lam,total_displacement,total_force,n_failed,n_active\n")
+        for k in range(n_done):
+            f.write(f"{k+1},{float(run['lam'][k])!r},{curve[k][0]!r},{curve[k][1]!r},"
+                    f"{int(run['n_failed'][k])},{int(run['n_active'][k])}\n")
+    if npy:
+        np.save(os.path.join(fea_dir, "event_of.npy"), run["event_of"])
+    if not n_done:
+        return [], [], [], []
+    return run["stress"], run["active"], run["U"], curve
+
+
 def write_records(fea_dir, n_nodes, n_elems, stress_record, active_record, disp_record,
                   force_disp_curve, out_format="python", npy=False):
     """CSV writers, src/fea_solver.py:297-316 (pandas) / src/fea_petsc.cpp:433-516,
@@ -337,6 +389,12 @@ def main(argv=None):
     ap.add_argument("--device-run", action="store_true",
                     help="run the step loop as one library call, the records gathered on the device "
                          "(one process, one partition)")
+    ap.add_argument("--events", action="store_true",
+                    help="event-driven failure run: one solve per failure, each break at its exact "
+                         "load (one process, one partition)")
+    ap.add_argument("--tie-rtol", type=float, default=1e-9,
+                    help="--events: elements within this relative distance of the largest strain break together")
+    ap.add_argument("--max-events", type=int, default=None, help="--events: at most this many events")
     ap.add_argument("--parts", type=int, default=1,
                     help="partitions of the multi-GPU solve, all on this device (one process); "
                          "for one GPU per process launch with torch.distributed.run instead")
@@ -345,7 +403,8 @@ def main(argv=None):
     fea_solver(a.results_dir, tol=a.grip_length, rtol=a.rtol, max_it=a.max_it,
                precond={"gamg": _capi.PC_GAMG, "jacobi": _capi.PC_JACOBI,
                         "bjacobi": _capi.PC_BLOCK_JACOBI, "sor": _capi.PC_SOR, "icc": _capi.PC_ICC}[a.pc],
-               out_format=a.format, nparts=a.parts, npy=a.npy, device_run=a.device_run)
+               out_format=a.format, nparts=a.parts, npy=a.npy, device_run=a.device_run,
+               events=a.events, tie_rtol=a.tie_rtol, max_events=a.max_events)
 
 
 if __name__ == "__main__":

@@ -7,4 +7,6 @@ from ._capi import (Engine, MfeaError, SolverFailure, SolveOpts, Stats, abi_vers
                     make_opts, PC_JACOBI, PC_BLOCK_JACOBI, PC_GAMG, PC_SOR, PC_ICC, NORM_PRECONDITIONED,
                     NORM_UNPRECONDITIONED, LIB_PATH, dist_unique_id,
                     GrowParams, grow_params, scaled_grow_params, grow_network,
-                    RunRecords, RUN_COMPLETE, RUN_NO_ACTIVE)
+                    RunRecords, RUN_COMPLETE, RUN_NO_ACTIVE,
+                    EventOpts, EventOut, EventRecords, event_opts, event_envelope,
+                    EVENTS_COMPLETE, EVENTS_LAMBDA_MAX, EVENTS_UNLOADED)

@@ -24,7 +24,7 @@ DEFAULT_OPTIONS = {"graph": 1, "phase_times": 0, "dist_graph": 1, "order": -1, "
                    "asm_kernel": 0, "spec_post": 1, "setup_entry": 1,
                    "batch_graph": 1, "step_graph": 0,
                    "graph_start": 1, "combo_graph": 1, "amg_a0_slot": 1, "run_register": 1,
-                   "keep_operator": 1}
+                   "keep_operator": 1, "event_scratch": 1}
 CG_KERNEL = {"auto": 0, "lanes": 1, "sell": 2}
 
 LIB_PATH = os.environ.get("MFEA_LIB", os.path.join(os.path.dirname(_HERE), "libmfea.so"))
@@ -41,6 +41,8 @@ PC_JACOBI, PC_BLOCK_JACOBI, PC_GAMG, PC_SOR, PC_ICC = 0, 1, 2, 3, 4
 NORM_UNPRECONDITIONED, NORM_PRECONDITIONED = 0, 1
 MESH_SKIP_INVALID = 1
 RUN_COMPLETE, RUN_NO_ACTIVE = 0, 1  # mfea_run's stop_reason (or EMAXIT / EBREAKDOWN)
+# mfea_run_events' stop_reason (or EMAXIT / EBREAKDOWN)
+EVENTS_COMPLETE, EVENTS_LAMBDA_MAX, EVENTS_UNLOADED = 0, 1, 2
 
 
 class SolveOpts(C.Structure):
@@ -63,6 +65,25 @@ class RunRecords(C.Structure):
     """mfea_run_records (include/mfea.h): where mfea_run writes each step's rows."""
     _fields_ = [("U", C.c_void_p), ("stress", C.c_void_p), ("active", C.c_void_p),
                 ("force", C.c_void_p), ("n_active", C.c_void_p), ("stats", C.POINTER(Stats)),
+                ("wall_s", C.c_void_p)]
+
+
+class EventOpts(C.Structure):
+    """mfea_event_opts (include/mfea.h)."""
+    _fields_ = [("max_strain", C.c_double), ("tie_rtol", C.c_double), ("lam_max", C.c_double)]
+
+
+class EventOut(C.Structure):
+    """mfea_event_out (include/mfea.h)."""
+    _fields_ = [("lam", C.c_double), ("force1", C.c_double), ("n_failed", C.c_int64),
+                ("n_active", C.c_int64)]
+
+
+class EventRecords(C.Structure):
+    """mfea_event_records (include/mfea.h): where mfea_run_events writes each event's rows."""
+    _fields_ = [("U", C.c_void_p), ("stress", C.c_void_p), ("active", C.c_void_p),
+                ("lam", C.c_void_p), ("force1", C.c_void_p), ("n_failed", C.c_void_p),
+                ("n_active", C.c_void_p), ("event_of", C.c_void_p), ("stats", C.POINTER(Stats)),
                 ("wall_s", C.c_void_p)]
 
 
@@ -113,6 +134,11 @@ _sig = {
                             C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(Stats)]),
     "mfea_run": (C.c_int, [_P, C.c_int32, _P, _P, C.POINTER(SolveOpts), C.c_double,
                            C.POINTER(RunRecords), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mfea_event": (C.c_int, [_P, C.c_double, C.c_double, C.POINTER(SolveOpts), C.POINTER(EventOpts),
+                             C.POINTER(EventOut), C.POINTER(Stats)]),
+    "mfea_run_events": (C.c_int, [_P, C.c_int32, C.c_double, C.c_double, C.POINTER(SolveOpts),
+                                  C.POINTER(EventOpts), C.POINTER(EventRecords), C.POINTER(C.c_int32),
+                                  C.POINTER(C.c_int32)]),
     "mfea_get_displacement": (C.c_int, [_P, _P]),
     "mfea_get_stress": (C.c_int, [_P, _P]),
     "mfea_get_active": (C.c_int, [_P, _P]),
@@ -291,6 +317,50 @@ def grow_network(params: GrowParams | None = None, out_dir=None):
 def make_opts(rtol=1e-8, atol=0.0, max_it=100000, precond=PC_JACOBI, norm=NORM_UNPRECONDITIONED,
               chunk=0, reg=1e-12) -> SolveOpts:
     return SolveOpts(rtol, atol, int(max_it), int(precond), int(norm), int(chunk), reg)
+
+
+def event_opts(max_strain, tie_rtol=1e-9, lam_max=np.inf) -> EventOpts:
+    """mfea_event_opts, checked as the library checks them."""
+    max_strain, tie_rtol, lam_max = float(max_strain), float(tie_rtol), float(lam_max)
+    if not max_strain > 0.0:
+        raise ValueError("max_strain must be > 0")
+    if not 0.0 <= tie_rtol < 1.0:
+        raise ValueError("tie_rtol must be in [0, 1)")
+    if not lam_max > 0.0:
+        raise ValueError("lam_max must be > 0 (inf allowed)")
+    return EventOpts(max_strain, tie_rtol, lam_max)
+
+
+def event_envelope(lam, force1, span):
+    """The displacement-controlled force-displacement sawtooth of an event run.
+
+    lam[k], force1[k]: load factor and reference-load reaction of event k;
+    span = dy_top - dy_bot of the reference load.  Under displacement control
+    the grips only ever move apart, so event k happens at the displacement
+    Lam_k·span with Lam_k = max(lam[0..k]): an event with lam[k] < Lam_{k-1}
+    is an avalanche break at held displacement.  Two points per event — the
+    force just before the break, Lam_k·force1[k], and just after it on the new
+    active set, Lam_k·force1[k+1] (the last event: Lam_k·force1[k], nothing
+    follows it).  A terminal event's lam (inf on an unloaded network, or one
+    beyond lam_max) is no displacement the test reached: Lam stays, and with it
+    the point.  Returns (displacement, force), arrays of 2·len(lam) entries.
+    """
+    lam = np.asarray(lam, dtype=np.float64).ravel()
+    f1 = np.asarray(force1, dtype=np.float64).ravel()
+    if lam.size != f1.size:
+        raise ValueError("lam and force1 must have one entry per event")
+    n = lam.size
+    disp = np.empty(2 * n)
+    force = np.empty(2 * n)
+    top = 0.0
+    for k in range(n):
+        if np.isfinite(lam[k]) and lam[k] > top:
+            top = float(lam[k])
+        nxt = f1[k + 1] if k + 1 < n else f1[k]
+        disp[2 * k] = disp[2 * k + 1] = top * span
+        force[2 * k] = top * f1[k]
+        force[2 * k + 1] = top * nxt
+    return disp, force
 
 
 class Engine:
@@ -473,6 +543,71 @@ class Engine:
             res["active"] = res["active"].astype(bool)
         res.update(force=force[:m], n_active=n_active[:m], stats=[stats[i].as_dict() for i in range(m)],
                    wall_s=wall[:m], n_done=m, stop_reason=stop.value)
+        return res
+
+    def event(self, dy_top, dy_bot, opts: SolveOpts | None, max_strain, tie_rtol=1e-9, lam_max=np.inf):
+        """One failure event at the reference load (mfea_event): returns
+        (lam, force1, n_failed, n_active, stats); n_failed == 0 is terminal."""
+        ev = event_opts(max_strain, tie_rtol, lam_max)
+        out = EventOut()
+        st = Stats()
+        o = opts if opts is not None else make_opts()
+        _check(_lib.mfea_event(self._h, float(dy_top), float(dy_bot), C.byref(o), C.byref(ev), C.byref(out),
+                               C.byref(st)), st)
+        return out.lam, out.force1, out.n_failed, out.n_active, st
+
+    def run_events(self, dy_top, dy_bot, opts: SolveOpts | None, max_strain, tie_rtol=1e-9, lam_max=np.inf,
+                   n_events=None, keep=("U", "stress", "active"), out=None):
+        """The event-driven failure run in one call (mfea_run_events): up to
+        n_events (default n_elems + 1) events at the reference load (dy_top,
+        dy_bot), each break at its exact load factor.  keep / out: as run().
+        Returns a dict: the records cut to [:n_done] (U rows = lam·U₁, active
+        as bool), lam, force1, n_failed, n_active, event_of (int32 per element,
+        -1 = never failed), stats, wall_s, n_done and stop_reason
+        (EVENTS_COMPLETE, EVENTS_LAMBDA_MAX, EVENTS_UNLOADED, EMAXIT or
+        EBREAKDOWN — a solver stop does not raise)."""
+        ev = event_opts(max_strain, tie_rtol, lam_max)
+        n = self.n_elems + 1 if n_events is None else int(n_events)
+        if n < 0:
+            raise ValueError("n_events must be >= 0")
+        unknown = set(keep) - {"U", "stress", "active"}
+        if unknown:
+            raise ValueError(f"unknown record(s) {sorted(unknown)}")
+        spec = {"U": (3 * self.n_nodes, np.float64), "stress": (self.n_elems, np.float64),
+                "active": (self.n_elems, np.uint8)}
+        arr = {}
+        for name, (cols, dt) in spec.items():
+            if name not in keep:
+                arr[name] = None
+                continue
+            a = (out or {}).get(name)
+            if a is None:
+                a = np.empty((n, cols), dtype=dt)
+            elif a.dtype != dt or a.shape != (n, cols) or not a.flags.c_contiguous:
+                raise ValueError(f"out[{name!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {(n, cols)}")
+            arr[name] = a
+        lam = np.zeros(n)
+        force1 = np.zeros(n)
+        n_failed = np.zeros(n, dtype=np.int64)
+        n_active = np.zeros(n, dtype=np.int64)
+        wall = np.zeros(n)
+        event_of = np.full(self.n_elems, -1, dtype=np.int32)
+        stats = (Stats * max(n, 1))()
+        rec = EventRecords(*(arr[k].ctypes.data if arr[k] is not None and arr[k].size else None
+                             for k in ("U", "stress", "active")),
+                           lam.ctypes.data, force1.ctypes.data, n_failed.ctypes.data, n_active.ctypes.data,
+                           event_of.ctypes.data if event_of.size else None, stats, wall.ctypes.data)
+        o = opts if opts is not None else make_opts()
+        n_done, stop = C.c_int32(), C.c_int32()
+        _check(_lib.mfea_run_events(self._h, n, float(dy_top), float(dy_bot), C.byref(o), C.byref(ev),
+                                    C.byref(rec), C.byref(n_done), C.byref(stop)))
+        m = n_done.value
+        res = {k: (None if a is None else a[:m]) for k, a in arr.items()}
+        if res["active"] is not None:
+            res["active"] = res["active"].astype(bool)
+        res.update(lam=lam[:m], force1=force1[:m], n_failed=n_failed[:m], n_active=n_active[:m],
+                   event_of=event_of, stats=[stats[i].as_dict() for i in range(m)], wall_s=wall[:m],
+                   n_done=m, stop_reason=stop.value)
         return res
 
     # ---- results --------------------------------------------------------------
