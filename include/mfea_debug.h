@@ -117,7 +117,8 @@ int mfea_debug_floating(mfea_handle* h, uint8_t* out);
  *                        the build and asm_kernel hold (only the RHS is formed), and keep the
  *                        GAMG hierarchy's values while K, the plan, the floating mask, reg
  *                        and ω hold (1; 0: assemble and set up every step).  Every other
- *                        option set drops both, but phase_times, run_register, amg_close and amg_start.
+ *                        option set drops both, but phase_times, run_register, amg_close, amg_start,
+ *                        amg_lazy_px and amg_big_chunk.
  *                        Read-only totals since mfea_create: "op_kept_steps" (steps that
  *                        skipped the assembly), "amg_setup_kept" (solves that skipped the
  *                        numeric setup) — mfea.h mfea_step, DESIGN.md §4.7
@@ -140,6 +141,20 @@ int mfea_debug_floating(mfea_handle* h, uint8_t* out);
  *                        k_amg_rhs, k_cg_init_finalize and k_amg_cg_init (0); the same bits.
  *                        Keeps K and the hierarchy's values when set.  Read-only
  *                        "amg_start_fused": solves that started with k_amg_start
+ *   "amg_lazy_px" 0|1    MFEA_PC_GAMG, one partition, a hierarchy of two levels or more: the
+ *                        update of an iteration moves s, r and level 0's x only, every V-cycle
+ *                        of a chunk keeps its output u in a slot of its own, and one replay at
+ *                        the chunk's end (in the closing check's launch, or its own) runs the
+ *                        p and x fma chains of the chunk's updates (1; 0: every update moves
+ *                        p and x).  The same bits.  Keeps K and the hierarchy's values when
+ *                        set.  SOR / ICC, one-level hierarchies and the partitioned solves run
+ *                        as with 0.  Read-only: "amg_px_slots" (u slots the hierarchy holds; a
+ *                        chunk of more groups replays whenever they are full),
+ *                        "amg_px_replays" (total since mfea_create of replay launches the
+ *                        solves queued) — DESIGN.md §4.10
+ *   "amg_big_chunk" n    MFEA_PC_GAMG, one partition, chunk 0 in the solve's options: groups per
+ *                        chunk of a planned batch that is not one graph of its own length
+ *                        (8; 2..63).  Keeps K and the hierarchy's values when set.
  * Read-only: "sweep_colors", "sweep_pieces" (the last SOR / ICC plan), "asm_colours"
  * (the element colouring's colours once asm_kernel 1 or 2 has run; 0 before).
  * Options that change the symbolic layout rebuild it at the next call. */

@@ -1500,14 +1500,83 @@ __global__ __launch_bounds__(BS) void k_amg_cg_w(int j, AmgLevD L0, AmgCg cg, Sl
   }
 }
 
+// The lazy p, x chain's replay (amg_kernels.hpp AmgPx).  The records of the
+// launch's updates that ran, compacted in update order (one wave: a ballot
+// and a prefix count), so the row loop below is unconditional loads and fmas.
+struct PxLive {
+  double alpha[kAmgPxSlots], beta[kAmgPxSlots];
+  int64_t off[kAmgPxSlots];  // the update's u slot, in floats from uh
+  int n;
+};
+__device__ __forceinline__ void px_records(const Slot* __restrict__ slots, const AmgPx& px, PxLive& L) {
+  if (threadIdx.x < 64) {
+    const int t = threadIdx.x, k = px.k0 + t;
+    bool run = false;
+    double a = 0.0, b = 0.0;
+    if (t < px.cnt) {
+      const Slot& rec = slots[k + 1];
+      run = rec.flag == kRun && rec.pad == 0;
+      a = rec.alpha;
+      b = rec.beta;
+    }
+    const unsigned long long m = __ballot(run);
+    if (run) {
+      const int q = __popcll(m & ((1ull << t) - 1ull));
+      L.alpha[q] = a;
+      L.beta[q] = b;
+      L.off[q] = (int64_t)amg_px_slot(k) * px.stride;
+    }
+    if (t == 0) L.n = __popcll(m);
+  }
+  __syncthreads();
+}
+// row i: the fat update's p = fma(β,p,u); x = fma(α,p,x) for each of them
+template <int ND>
+__device__ __forceinline__ void px_row(const AmgCg& cg, const AmgPx& px, const PxLive& L, int64_t i) {
+  const int n = L.n;
+  if (n == 0) return;
+  double p[ND], x[ND];
+  vload<ND>(cg.p, i, p);
+  vload<ND>(cg.x, i, x);
+#pragma unroll 4
+  for (int t = 0; t < n; ++t) {
+    double u[ND];
+    vload<ND>(px.uh + L.off[t], i, u);
+    const double alpha = L.alpha[t], beta = L.beta[t];
+#pragma unroll
+    for (int a = 0; a < ND; ++a) {
+      p[a] = fma(beta, p[a], u[a]);
+      x[a] = fma(alpha, p[a], x[a]);
+    }
+  }
+  vstore<ND>(cg.p, i, p);
+  vstore<ND>(cg.x, i, x);
+}
+// … as a launch of its own (no closing check behind the chunk, or a chunk
+// longer than the slots): the update's grid-stride row mapping
+template <int ND>
+__global__ __launch_bounds__(kCgBS) void k_amg_px_replay(AmgCg cg, const Slot* slots, AmgPx px) {
+  __shared__ PxLive live;
+  px_records(slots, px, live);
+  const int64_t stride = (int64_t)gridDim.x * kCgBS;
+  for (int64_t i = cg.lo + (int64_t)blockIdx.x * kCgBS + threadIdx.x; i < cg.hi; i += stride)
+    px_row<ND>(cg, px, live, i);
+}
+
 // The closing check of a chunk (cg.hip k_cg_advance): block partials of ‖r‖²
 // alone, without the V-cycle and w = A u whose launch would form them next.
 // The w kernel's block size, grid, row mapping, per-thread row order and fma
 // chain: partial b is bit for bit the acc[2] partial of the next w launch.
 // cpart: a buffer of its own, [4][kCgMaxG] as one parity of `part` (the w
 // and update launches of a continuing chunk find theirs untouched).
-template <int ND, int BS>
-__global__ __launch_bounds__(BS) void k_amg_rnorm(AmgCg cg, double* cpart) {
+//
+// REPLAY (option amg_lazy_px): each row also runs the chunk's p, x chain
+// (px_row) — own-row work on other arrays, behind the row's load of r; the
+// ‖r‖² chain and its partials are untouched.
+template <int ND, int BS, bool REPLAY = false>
+__global__ __launch_bounds__(BS) void k_amg_rnorm(AmgCg cg, double* cpart, const Slot* slots, AmgPx px) {
+  __shared__ PxLive live;
+  if constexpr (REPLAY) px_records(slots, px, live);
   double acc[4] = {0.0, 0.0, 0.0, 0.0};
   const int64_t stride = (int64_t)gridDim.x * BS;
   const int lane = threadIdx.x & 63;
@@ -1515,6 +1584,7 @@ __global__ __launch_bounds__(BS) void k_amg_rnorm(AmgCg cg, double* cpart) {
     if (i < cg.lo || i >= cg.hi) continue;
     double r[ND];
     vload<ND>(cg.r, i, r);
+    if constexpr (REPLAY) px_row<ND>(cg, px, live, i);
 #pragma unroll
     for (int a = 0; a < ND; ++a) acc[2] = fma(r[a], r[a], acc[2]);
   }
@@ -1556,7 +1626,10 @@ __global__ __launch_bounds__(kBlock) void k_amg_pack_u(AmgCg cg, AmgDist d) {
   for (int a = 0; a < ND; ++a) d.usend[ND * k + a] = i >= 0 ? cg.u[ND * i + a] : 0.0;
 }
 
-template <int ND, int PU, int BS, bool DIST>
+// LAZY (option amg_lazy_px; !DIST, level 0 forms its x here): the slim form —
+// u, p and x are neither loaded nor stored, the chunk's replay moves p and x
+// (px_row); everything else is the fat form's
+template <int ND, int PU, int BS, bool DIST, bool LAZY = false>
 __global__ __launch_bounds__(BS) void k_amg_cg_update(int j, AmgLevD L0, AmgCg cg, Slot* slots,
                                                       SolveState* st, double* part, AmgDist d) {
   const int f0 = __builtin_nontemporal_load(&slots[j].flag);
@@ -1586,11 +1659,11 @@ __global__ __launch_bounds__(BS) void k_amg_cg_update(int j, AmgLevD L0, AmgCg c
   float Di[ND * ND];
   if (cg.hi > cg.lo) {
     const int64_t k = i0 < cg.hi ? i0 : cg.hi - 1;
-    vload<ND>(cg.u, k, u);
+    if constexpr (!LAZY) vload<ND>(cg.u, k, u);
     vload<ND>(cg.w, k, w);
-    vload<ND>(cg.p, k, p);
+    if constexpr (!LAZY) vload<ND>(cg.p, k, p);
     vload<ND>(cg.s, k, s);
-    vload<ND>(cg.x, k, x);
+    if constexpr (!LAZY) vload<ND>(cg.x, k, x);
     vload<ND>(cg.r, k, r);
     if (x0_here) dinv_load<ND>(L0.dinv32, k, Di);
   }
@@ -1610,24 +1683,24 @@ __global__ __launch_bounds__(BS) void k_amg_cg_update(int j, AmgLevD L0, AmgCg c
   const double alpha = cs.alpha, beta = cs.beta;
   for (int64_t i = i0; i < cg.hi; i += stride) {
     if (i != i0) {
-      vload<ND>(cg.u, i, u);
+      if constexpr (!LAZY) vload<ND>(cg.u, i, u);
       vload<ND>(cg.w, i, w);
-      vload<ND>(cg.p, i, p);
+      if constexpr (!LAZY) vload<ND>(cg.p, i, p);
       vload<ND>(cg.s, i, s);
-      vload<ND>(cg.x, i, x);
+      if constexpr (!LAZY) vload<ND>(cg.x, i, x);
       vload<ND>(cg.r, i, r);
       if (x0_here) dinv_load<ND>(L0.dinv32, i, Di);
     }
 #pragma unroll
     for (int a = 0; a < ND; ++a) {
-      p[a] = fma(beta, p[a], u[a]);
+      if constexpr (!LAZY) p[a] = fma(beta, p[a], u[a]);
       s[a] = fma(beta, s[a], w[a]);
-      x[a] = fma(alpha, p[a], x[a]);
+      if constexpr (!LAZY) x[a] = fma(alpha, p[a], x[a]);
       r[a] = fma(-alpha, s[a], r[a]);
     }
-    vstore<ND>(cg.p, i, p);
+    if constexpr (!LAZY) vstore<ND>(cg.p, i, p);
     vstore<ND>(cg.s, i, s);
-    vstore<ND>(cg.x, i, x);
+    if constexpr (!LAZY) vstore<ND>(cg.x, i, x);
     vstore<ND>(cg.r, i, r);
     if (x0_here) {  // level 0's x = ω D⁻¹ r (vcycle_entry's arithmetic)
       float rf[ND], x0[ND];
@@ -2158,22 +2231,34 @@ void launch_amg_cg_w(hipStream_t s, int nd, int j, bool first, const AmgLevD& L0
 }
 
 // the w kernel's launch geometry (w_nd / w_bs), so the partials match its own
-template <int ND>
-static void rnorm_nd(hipStream_t s, const AmgCg& cg, double* cpart) {
+template <int ND, bool REPLAY>
+static void rnorm_nd(hipStream_t s, const AmgCg& cg, double* cpart, const Slot* slots, const AmgPx& px) {
   const dim3 g((unsigned)amg_w_grid(cg));
   switch (amg_w_block(cg)) {
-    case 512: hipLaunchKernelGGL((k_amg_rnorm<ND, 512>), g, dim3(512), 0, s, cg, cpart); break;
-    case 576: hipLaunchKernelGGL((k_amg_rnorm<ND, 576>), g, dim3(576), 0, s, cg, cpart); break;
-    case 640: hipLaunchKernelGGL((k_amg_rnorm<ND, 640>), g, dim3(640), 0, s, cg, cpart); break;
-    case 704: hipLaunchKernelGGL((k_amg_rnorm<ND, 704>), g, dim3(704), 0, s, cg, cpart); break;
-    case 768: hipLaunchKernelGGL((k_amg_rnorm<ND, 768>), g, dim3(768), 0, s, cg, cpart); break;
-    case 1024: hipLaunchKernelGGL((k_amg_rnorm<ND, 1024>), g, dim3(1024), 0, s, cg, cpart); break;
-    default: hipLaunchKernelGGL((k_amg_rnorm<ND, kCgBS>), g, dim3(kCgBS), 0, s, cg, cpart); break;
+    case 512: hipLaunchKernelGGL((k_amg_rnorm<ND, 512, REPLAY>), g, dim3(512), 0, s, cg, cpart, slots, px); break;
+    case 576: hipLaunchKernelGGL((k_amg_rnorm<ND, 576, REPLAY>), g, dim3(576), 0, s, cg, cpart, slots, px); break;
+    case 640: hipLaunchKernelGGL((k_amg_rnorm<ND, 640, REPLAY>), g, dim3(640), 0, s, cg, cpart, slots, px); break;
+    case 704: hipLaunchKernelGGL((k_amg_rnorm<ND, 704, REPLAY>), g, dim3(704), 0, s, cg, cpart, slots, px); break;
+    case 768: hipLaunchKernelGGL((k_amg_rnorm<ND, 768, REPLAY>), g, dim3(768), 0, s, cg, cpart, slots, px); break;
+    case 1024: hipLaunchKernelGGL((k_amg_rnorm<ND, 1024, REPLAY>), g, dim3(1024), 0, s, cg, cpart, slots, px); break;
+    default: hipLaunchKernelGGL((k_amg_rnorm<ND, kCgBS, REPLAY>), g, dim3(kCgBS), 0, s, cg, cpart, slots, px); break;
   }
 }
 void launch_amg_rnorm(hipStream_t s, int nd, const AmgCg& cg, double* cpart) {
-  if (nd == 2) rnorm_nd<2>(s, cg, cpart);
-  else rnorm_nd<3>(s, cg, cpart);
+  if (nd == 2) rnorm_nd<2, false>(s, cg, cpart, nullptr, AmgPx{});
+  else rnorm_nd<3, false>(s, cg, cpart, nullptr, AmgPx{});
+}
+void launch_amg_rnorm_px(hipStream_t s, int nd, const AmgCg& cg, double* cpart, const Slot* slots,
+                         const AmgPx& px) {
+  if (nd == 2) rnorm_nd<2, true>(s, cg, cpart, slots, px);
+  else rnorm_nd<3, true>(s, cg, cpart, slots, px);
+}
+void launch_amg_px_replay(hipStream_t s, int nd, const AmgCg& cg, const Slot* slots, const AmgPx& px) {
+  if (cg.hi <= cg.lo) return;
+  int64_t g = (cg.hi - cg.lo + kCgBS - 1) / kCgBS;  // (the update's grid, upd_bs)
+  g = g > kCgMaxG ? kCgMaxG : g;
+  if (nd == 2) hipLaunchKernelGGL(k_amg_px_replay<2>, dim3((unsigned)g), dim3(kCgBS), 0, s, cg, slots, px);
+  else hipLaunchKernelGGL(k_amg_px_replay<3>, dim3((unsigned)g), dim3(kCgBS), 0, s, cg, slots, px);
 }
 
 void launch_amg_gsum(hipStream_t s, const AmgCg& cg, const double* part_q, const AmgDist& d, int q) {
@@ -2193,7 +2278,7 @@ void launch_amg_pack_u(hipStream_t s, int nd, const AmgCg& cg, const AmgDist& d)
   else hipLaunchKernelGGL(k_amg_pack_u<3>, rows_grid(d.n_send), dim3(kBlock), 0, s, cg, d);
 }
 
-template <int ND, int BS, bool DIST>
+template <int ND, int BS, bool DIST, bool LAZY = false>
 static void upd_bs(hipStream_t s, int j, const AmgLevD& L0, const AmgCg& cg, Slot* slots,
                    SolveState* st, double* part, const AmgDist& d) {
   const int64_t gw = amg_w_grid(cg);  // partials to reduce = the w kernel's blocks
@@ -2201,22 +2286,24 @@ static void upd_bs(hipStream_t s, int j, const AmgLevD& L0, const AmgCg& cg, Slo
   gu = gu < 1 ? 1 : (gu > kCgMaxG ? kCgMaxG : gu);
   const dim3 g((unsigned)gu);
   switch (DIST ? 1 : pu_of_grid(gw)) {
-    case 1: hipLaunchKernelGGL((k_amg_cg_update<ND, 1, BS, DIST>), g, dim3(BS), 0, s, j, L0, cg, slots, st, part, d); break;
-    case 2: hipLaunchKernelGGL((k_amg_cg_update<ND, 2, BS, DIST>), g, dim3(BS), 0, s, j, L0, cg, slots, st, part, d); break;
-    case 4: hipLaunchKernelGGL((k_amg_cg_update<ND, 4, BS, DIST>), g, dim3(BS), 0, s, j, L0, cg, slots, st, part, d); break;
-    default: hipLaunchKernelGGL((k_amg_cg_update<ND, 8, BS, DIST>), g, dim3(BS), 0, s, j, L0, cg, slots, st, part, d); break;
+    case 1: hipLaunchKernelGGL((k_amg_cg_update<ND, 1, BS, DIST, LAZY>), g, dim3(BS), 0, s, j, L0, cg, slots, st, part, d); break;
+    case 2: hipLaunchKernelGGL((k_amg_cg_update<ND, 2, BS, DIST, LAZY>), g, dim3(BS), 0, s, j, L0, cg, slots, st, part, d); break;
+    case 4: hipLaunchKernelGGL((k_amg_cg_update<ND, 4, BS, DIST, LAZY>), g, dim3(BS), 0, s, j, L0, cg, slots, st, part, d); break;
+    default: hipLaunchKernelGGL((k_amg_cg_update<ND, 8, BS, DIST, LAZY>), g, dim3(BS), 0, s, j, L0, cg, slots, st, part, d); break;
   }
 }
 template <int ND>
 static void upd_nd(hipStream_t s, int j, const AmgLevD& L0, const AmgCg& cg, Slot* slots,
-                   SolveState* st, double* part, const AmgDist* d) {
+                   SolveState* st, double* part, const AmgDist* d, bool lazy) {
   if (d) upd_bs<ND, kCgBS, true>(s, j, L0, cg, slots, st, part, *d);
+  else if (lazy) upd_bs<ND, kCgBS, false, true>(s, j, L0, cg, slots, st, part, AmgDist{});
   else upd_bs<ND, kCgBS, false>(s, j, L0, cg, slots, st, part, AmgDist{});
 }
 void launch_amg_cg_update(hipStream_t s, int nd, int j, const AmgLevD& L0, const AmgCg& cg, Slot* slots,
-                          SolveState* st, double* part, const AmgDist* d) {
-  if (nd == 2) upd_nd<2>(s, j, L0, cg, slots, st, part, d);
-  else upd_nd<3>(s, j, L0, cg, slots, st, part, d);
+                          SolveState* st, double* part, const AmgDist* d, bool lazy) {
+  lazy = lazy && !d && !cg.sweep && !L0.coarsest;  // (level 0 forms its x in the update: x0_here)
+  if (nd == 2) upd_nd<2>(s, j, L0, cg, slots, st, part, d, lazy);
+  else upd_nd<3>(s, j, L0, cg, slots, st, part, d, lazy);
 }
 
 void launch_amg_finish(hipStream_t s, int nd, const AmgCg& cg, double* x_row) {

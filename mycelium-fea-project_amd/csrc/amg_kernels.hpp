@@ -318,15 +318,39 @@ void launch_amg_start(hipStream_t s, int nd, const SellOp& op, const uint8_t* co
 // block partials of ‖r‖² alone, bitwise the next w launch's (component 2 of
 // cpart = [4][kCgMaxPartials]): the closing check of a chunk, launch_cg_advance
 void launch_amg_rnorm(hipStream_t s, int nd, const AmgCg& cg, double* cpart);
+// The lazy p, x chain (option amg_lazy_px).  Nothing in an iteration reads p
+// or x: the slim update leaves them alone, every V-cycle of a chunk stores its
+// u in a slot of its own, and a replay at the chunk's end runs
+// p = fma(β_k, p, u_k); x = fma(α_k, p, x) for the chunk's updates k in order
+// — the fat update's fma chains on its operands, so p and x get its bits.
+// Update k's record is slots[k + 1]; it is replayed when its flag is kRun
+// and its pad 0 (k_cg_advance marks the record it rolls over: that update
+// was replayed by the chunk before).  Update 0 (the entry's) owns slot 0,
+// update k ≥ 1 slot 1 + (k − 1) mod (kAmgPxSlots − 1): a chunk longer than
+// that replays whenever the slots are full.
+constexpr int kAmgPxSlots = 17;
+struct AmgPx {
+  const float* uh = nullptr;  // kAmgPxSlots slots of `stride` floats
+  int64_t stride = 0;
+  int k0 = 0;   // first update of this replay
+  int cnt = 0;  // updates k0 … k0 + cnt − 1 (≤ kAmgPxSlots)
+};
+__host__ __device__ inline int amg_px_slot(int k) { return k == 0 ? 0 : 1 + (k - 1) % (kAmgPxSlots - 1); }
+// … as independent own-row work of the closing check's launch
+void launch_amg_rnorm_px(hipStream_t s, int nd, const AmgCg& cg, double* cpart, const Slot* slots,
+                         const AmgPx& px);
+// … or as a launch of its own
+void launch_amg_px_replay(hipStream_t s, int nd, const AmgCg& cg, const Slot* slots, const AmgPx& px);
 // partitioned: this rank's block partials of parity q → gall[q] row rank, gsend
 void launch_amg_gsum(hipStream_t s, const AmgCg& cg, const double* part_q, const AmgDist& d, int q);
 // partitioned: u of the send rows → usend
 void launch_amg_pack_u(hipStream_t s, int nd, const AmgCg& cg, const AmgDist& d);
 // iteration j: α, β from the partials (d: from the gathered rank sums), p s x
-// r update, level-0 x = ω D⁻¹ r
+// r update, level-0 x = ω D⁻¹ r (lazy: the slim form, s r and level-0 x only;
+// one partition with a level below level 0)
 void launch_amg_cg_update(hipStream_t s, int nd, int j, const AmgLevD& L0, const AmgCg& cg,
                           Slot* slots, SolveState* st, double* part,
-                          const AmgDist* d = nullptr);
+                          const AmgDist* d = nullptr, bool lazy = false);
 // x (level-0 order, ND per row) → row-order x[3·row + c]
 void launch_amg_finish(hipStream_t s, int nd, const AmgCg& cg, double* x_row);
 // grid of the w kernel (its partials are re-read by the update kernel)

@@ -195,6 +195,10 @@ struct Part {
   int amg_tail = 0;                  // first level of the single-workgroup tail (0: none)
   int amg_first = 1;                 // first level the four-step tail may start at (not split)
   AmgCg amg_cg;
+  // the V-cycle outputs u of a chunk, one slot per update (option amg_lazy_px,
+  // amg_kernels.hpp AmgPx); null: partitioned or a one-level plan
+  float* amg_uh = nullptr;
+  int64_t amg_uh_stride = 0;
   // the plan's preconditioner kind: MFEA_PC_GAMG (the hierarchy) or a
   // one-level plan with multicolour sweeps (MFEA_PC_SOR / MFEA_PC_ICC, sweep.hip)
   int amg_kind = MFEA_PC_GAMG;
@@ -350,6 +354,10 @@ struct mfea_handle {
   // RHS, the CG's state and level-0 b) instead of three.  0: the three.
   int opt_amg_start = 1;
   int64_t amg_start_fused = 0;    // read-only option: solves that started with k_amg_start
+  // The update moves s, r and level 0's x only; p and x are replayed from the
+  // chunk's kept u at its end (amg_kernels.hpp AmgPx).  0: the fat update.
+  int opt_amg_lazy_px = 1;
+  int64_t amg_px_replays = 0;     // read-only option: replay launches queued by the solves
   bool setup_skipped = false;     // the last solve did (phase times: t_setup_ms = 0)
   Material graph_batch_mat{};     // the material graph_batch's post kernels were captured with
   bool asm_pending = false;  // mfea_step deferred its assembly to solve_amg
@@ -1707,6 +1715,8 @@ int upload_amg(mfea_handle* h, Part& pt, const AmgPlan& pl, const AmgRank* rk = 
     pt.amg_cg.w = D((size_t)nd * nf);
     pt.amg_cg.r = D((size_t)nd * nf);
     pt.amg_cg.u = F((size_t)nd * nf);
+    pt.amg_uh_stride = (int64_t)amg_al((size_t)nd * nf);
+    pt.amg_uh = !rk && nlev > 1 ? F((size_t)kAmgPxSlots * pt.amg_uh_stride) : nullptr;
     // the merged levels' operators, lists and vector buffer
     pt.amg_mg = AmgMergeD{};
     if (pt.amg_mplan.on) {
@@ -1888,11 +1898,36 @@ int upload_sweep(mfea_handle* h, Part& pt, int kind) {
 
 // the preconditioner application u = M r of one PCG iteration (gate: its
 // flag; NULL: ungated)
-void launch_precond(mfea_handle* h, Part& pt, const int32_t* gate) {
-  if (pt.amg_cg.sweep) launch_sweep(h->stream, pt.amg.nd, pt.swd, pt.amg_cg, gate);
-  else launch_amg_vcycle(h->stream, pt.amg.nd, pt.amg_lev.data(), (int)pt.amg_lev.size(), pt.amg_cg, pt.amg_tail, gate,
+// (cg: pt.amg_cg with another u, the lazy p, x chain's slot — px_cg)
+void launch_precond(mfea_handle* h, Part& pt, const int32_t* gate, const AmgCg* cg) {
+  const AmgCg& c = cg ? *cg : pt.amg_cg;
+  if (pt.amg_cg.sweep) launch_sweep(h->stream, pt.amg.nd, pt.swd, c, gate);
+  else launch_amg_vcycle(h->stream, pt.amg.nd, pt.amg_lev.data(), (int)pt.amg_lev.size(), c, pt.amg_tail, gate,
                          0, pt.amg_mg.on ? &pt.amg_mg : nullptr);
 }
+
+// The lazy p, x chain (option amg_lazy_px, amg_kernels.hpp AmgPx): the
+// one-partition GAMG solve whose level 0 forms its x in the update
+bool amg_lazy(const mfea_handle* h, const Part& pt) {
+  return h->opt_amg_lazy_px && pt.amg_uh && !pt.amg_cg.sweep && !pt.amg_lev.empty() && !pt.amg_lev[0].coarsest;
+}
+// the CG's arrays with update k's slot as u: what its V-cycle writes and its
+// w = A u reads (a host constant of each launch)
+AmgCg px_cg(const Part& pt, int k) {
+  AmgCg c = pt.amg_cg;
+  c.u = pt.amg_uh + (int64_t)amg_px_slot(k) * pt.amg_uh_stride;
+  return c;
+}
+AmgPx px_of(const Part& pt, int k0, int cnt) {
+  AmgPx px;
+  px.uh = pt.amg_uh;
+  px.stride = pt.amg_uh_stride;
+  px.k0 = k0;
+  px.cnt = cnt;
+  return px;
+}
+// replay launches of a chunk of `chunk` groups (enqueue_amg_chunk)
+int px_replays(int chunk) { return 1 + (chunk > 0 ? (chunk - 1) / (kAmgPxSlots - 1) : 0); }
 
 // (Re)build the hierarchy when the active set differs from the plan's.  One
 // partition: the host view of the activity (downloaded only when a post
@@ -2011,10 +2046,14 @@ void enqueue_amg_iteration(mfea_handle* h, Part& pt, int j, bool profile) {
   hipStream_t s = h->stream;
   const int nd = pt.amg.nd;
   const AmgLevD& L0 = pt.amg_lev[0];
-  launch_amg_cg_update(s, nd, j, L0, pt.amg_cg, pt.slots.ptr, pt.state.ptr, pt.cg_part.ptr);
+  // (the default form: the slim update, u in its slot — the replay, once a
+  // chunk, is not part of an iteration)
+  const bool lazy = amg_lazy(h, pt);
+  const AmgCg cg = lazy ? px_cg(pt, j) : pt.amg_cg;
+  launch_amg_cg_update(s, nd, j, L0, cg, pt.slots.ptr, pt.state.ptr, pt.cg_part.ptr, nullptr, lazy);
   (void)profile;
-  launch_precond(h, pt, nullptr);
-  launch_amg_cg_w(s, nd, j, profile, L0, pt.amg_cg, pt.slots.ptr, pt.cg_part.ptr);
+  launch_precond(h, pt, nullptr, &cg);
+  launch_amg_cg_w(s, nd, j, profile, L0, cg, pt.slots.ptr, pt.cg_part.ptr);
 }
 
 // ---- partitioned GAMG exchanges -------------------------------------------
@@ -2142,12 +2181,32 @@ void enqueue_amg_chunk(mfea_handle* h, Part& pt, int chunk, bool close) {
   // is a pure function of those — it rewrites the values it wrote before.  A
   // gate flag cost each launch a load from another XCD's L2 ahead of its
   // first wait (vector loads complete in order), ≈ 1 µs per launch.
+  //
+  // The lazy p, x chain (amg_lazy_px): the V-cycle of update k writes its u
+  // to slot amg_px_slot(k), so past the stop the chunk's remaining V-cycles
+  // write those same values into later slots instead of one buffer.  The
+  // replay reads only the slots of updates whose record says they ran, and
+  // every update past the stop records kStop: harmless.  The replay sits
+  // behind the chunk's last update — in the closing check's launch, else a
+  // launch of its own — and before the advance rolls the records over; a
+  // chunk longer than the slots replays whenever they are full.  k0: the
+  // first update not yet replayed (update 0 is the entry's; in a later chunk
+  // slots[1] is the rolled-over record, which the replay skips).
+  const bool lazy = amg_lazy(h, pt);
+  int k0 = 0;
   for (int j = 0; j < chunk; ++j) {
-    launch_precond(h, pt, nullptr);
-    launch_amg_cg_w(s, nd, j, false, L0, pt.amg_cg, pt.slots.ptr, pt.cg_part.ptr);
-    launch_amg_cg_update(s, nd, j + 1, L0, pt.amg_cg, pt.slots.ptr, pt.state.ptr, pt.cg_part.ptr);
+    const AmgCg cg = lazy ? px_cg(pt, j + 1) : pt.amg_cg;
+    launch_precond(h, pt, nullptr, &cg);
+    launch_amg_cg_w(s, nd, j, false, L0, cg, pt.slots.ptr, pt.cg_part.ptr);
+    launch_amg_cg_update(s, nd, j + 1, L0, cg, pt.slots.ptr, pt.state.ptr, pt.cg_part.ptr, nullptr, lazy);
+    if (lazy && (j + 1) % (kAmgPxSlots - 1) == 0 && j + 1 < chunk) {
+      launch_amg_px_replay(s, nd, pt.amg_cg, pt.slots.ptr, px_of(pt, k0, j + 2 - k0));
+      k0 = j + 2;
+    }
   }
-  if (close) launch_amg_rnorm(s, nd, pt.amg_cg, cg_part_buf(pt, 2));
+  if (lazy && close) launch_amg_rnorm_px(s, nd, pt.amg_cg, cg_part_buf(pt, 2), pt.slots.ptr, px_of(pt, k0, chunk + 1 - k0));
+  else if (lazy) launch_amg_px_replay(s, nd, pt.amg_cg, pt.slots.ptr, px_of(pt, k0, chunk + 1 - k0));
+  else if (close) launch_amg_rnorm(s, nd, pt.amg_cg, cg_part_buf(pt, 2));
   launch_cg_advance(s, chunk, pt.slots.ptr, pt.state.ptr, pt.mirror, 1, close ? cg_part_buf(pt, 2) : nullptr,
                     close ? (int)amg_w_grid(pt.amg_cg) : 0);
 }
@@ -2190,7 +2249,6 @@ uint64_t fnv1a(uint64_t k, const void* p, size_t n) {
   return k;
 }
 
-void launch_precond(mfea_handle* h, Part& pt, const int32_t* gate);
 int enqueue_post_work(mfea_handle* h, double max_strain);
 
 // The solve's entry behind the setup: level-0 b from the CG's r, the first
@@ -2201,9 +2259,11 @@ void enqueue_amg_entry(mfea_handle* h, Part& pt, bool skip_init = false) {
   const int nd = pt.amg.nd;
   const AmgLevD& L0 = pt.amg_lev[0];
   if (!skip_init) launch_amg_cg_init(s, nd, L0, pt.amg_cg, cg_vecs(pt).r[0]);
-  launch_precond(h, pt, nullptr);
-  launch_amg_cg_w(s, nd, 0, true, L0, pt.amg_cg, pt.slots.ptr, pt.cg_part.ptr);
-  launch_amg_cg_update(s, nd, 0, L0, pt.amg_cg, pt.slots.ptr, pt.state.ptr, pt.cg_part.ptr);  // update 0
+  const bool lazy = amg_lazy(h, pt);  // (update 0's u in slot 0: the first chunk's replay applies it)
+  const AmgCg cg = lazy ? px_cg(pt, 0) : pt.amg_cg;
+  launch_precond(h, pt, nullptr, &cg);
+  launch_amg_cg_w(s, nd, 0, true, L0, cg, pt.slots.ptr, pt.cg_part.ptr);
+  launch_amg_cg_update(s, nd, 0, L0, cg, pt.slots.ptr, pt.state.ptr, pt.cg_part.ptr, nullptr, lazy);  // update 0
 }
 
 // mfea_step's deferred assembly (option step_graph) at the head of the setup
@@ -2273,6 +2333,9 @@ int launch_amg_setup_graph(mfea_handle* h, Part& pt, double reg, uint64_t k0, bo
     k = fnv1a(k, &pt.amg_kind, sizeof pt.amg_kind);
     const int si = skip_init ? 1 : 0;
     k = fnv1a(k, &si, sizeof si);
+    const int lz = amg_lazy(h, pt) ? 1 : 0;
+    k = fnv1a(k, &lz, sizeof lz);
+    k = fnv1a(k, &pt.amg_uh, sizeof pt.amg_uh);
   }
   if (start) {  // the CG start (k_cg_init_finalize) at the graph's head
     const double sd[3] = {start->rtol, start->atol, start->reg};
@@ -2435,7 +2498,10 @@ int solve_amg(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opt
   const bool close = h->opt_amg_close && o->norm == MFEA_NORM_UNPRECONDITIONED && pt.amg_kind == MFEA_PC_GAMG;
   // (every cached chunk graph is tagged: the two chunk forms never mix)
   // (−4,000,000: below the partitioned forms' ranges, −2,000,000 − x and −3,000,000 − x)
-  const int tag = -1000 - (int)(pt.amg_gen % 1000000) - (close ? 4000000 : 0);
+  // (lazy p, x: −8,000,000 more, so the four forms' ranges stay apart)
+  const bool lazy = amg_lazy(h, pt);
+  const int tag = -1000 - (int)(pt.amg_gen % 1000000) - (close ? 4000000 : 0) - (lazy ? 8000000 : 0);
+  int64_t replays = 0;  // replay launches queued (read-only option amg_px_replays)
   // the converging update is iteration `iters`; update 0 ran in the entry, so
   // `iters` more groups (V-cycle, w, update) reach it: need.  With the closing
   // check the batch ends one group earlier, behind update iters − 1, and its
@@ -2489,6 +2555,7 @@ int solve_amg(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opt
                        [&]() -> int {
                          enqueue_amg_chunk(h, pt, chunk, close);
                          cycles += chunk;
+                         if (lazy) replays += px_replays(chunk);
                          HIPC(hipGetLastError());
                          return 0;
                        },
@@ -2566,11 +2633,13 @@ int solve_amg(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opt
                        [&]() -> int {
                          if (!combo) HIPC(hipGraphLaunch(h->graph_batch[need], s));  // (combo: launched with the setup)
                          cycles += need;
+                         if (lazy) replays += px_replays(need);
                          return 0;
                        },
                        [&](int n) -> int {
                          HIPC(hipGraphLaunch(h->graph, s));
                          cycles += n;
+                         if (lazy) replays += px_replays(chunk);
                          return 0;
                        },
                        &fin, finish, combo);
@@ -2582,11 +2651,13 @@ int solve_amg(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opt
                        [&](int n) -> int {
                          HIPC(hipGraphLaunch(n == chunk ? h->graph : n == big ? h->graph_big : h->graph_rem[n], s));
                          cycles += n;
+                         if (lazy) replays += px_replays(n);
                          return 0;
                        },
                        &fin, finish, exact_rem, close);
     }
   }
+  h->amg_px_replays += replays;
   if (rc) return rc;
   h->amg_last_cycles = cycles;
   if (fin.status == 0 && fin.closed) ++h->amg_close_hits;
@@ -4987,11 +5058,19 @@ int mfea_set_option(mfea_handle* h, const char* name, int64_t value) {
     if (value != 0 && value != 1) return fail(MFEA_EINVAL, "amg_start: 0 or 1");
     h->opt_amg_start = (int)value;
   }
+  else if (n == "amg_lazy_px") {
+    if (value != 0 && value != 1) return fail(MFEA_EINVAL, "amg_lazy_px: 0 or 1");
+    h->opt_amg_lazy_px = (int)value;
+  }
+  else if (n == "amg_big_chunk") {
+    if (value < 2 || value >= mfea_handle::kRemGraphs) return fail(MFEA_EINVAL, "amg_big_chunk: 2..63");
+    h->opt_amg_big_chunk = (int)value;
+  }
   else return fail(MFEA_EINVAL, "unknown option " + n);
   // kept K / hierarchy values: dropped by every option but the few that
   // cannot change a value (conservative: most options only change launches)
   if (n != "phase_times" && n != "run_register" && !(n == "keep_operator" && value == 1) &&
-      n != "amg_close" && n != "amg_start")
+      n != "amg_close" && n != "amg_start" && n != "amg_lazy_px" && n != "amg_big_chunk")
     drop_kept(h);
   destroy_graph(h);  // captured graphs hold the old geometry
   if (rebuild) {
@@ -5205,6 +5284,10 @@ int mfea_get_option(mfea_handle* h, const char* name, int64_t* value) {
   else if (n == "amg_setup_kept") *value = h->amg_setup_kept;  // read-only: solves that skipped the numeric setup
   else if (n == "amg_close") *value = h->opt_amg_close;
   else if (n == "amg_start") *value = h->opt_amg_start;
+  else if (n == "amg_lazy_px") *value = h->opt_amg_lazy_px;
+  else if (n == "amg_big_chunk") *value = h->opt_amg_big_chunk;
+  else if (n == "amg_px_replays") *value = h->amg_px_replays;  // read-only: p, x replay launches the solves queued
+  else if (n == "amg_px_slots") *value = kAmgPxSlots;          // read-only: u slots of the lazy p, x chain
   else if (n == "amg_start_fused") *value = h->amg_start_fused;  // read-only: solves that started with k_amg_start
   else if (n == "amg_close_hits") *value = h->amg_close_hits;    // read-only: solves ended by the closing check
   else if (n == "amg_last_cycles") *value = h->amg_last_cycles;  // read-only: V-cycle applications the last solve queued

@@ -468,6 +468,7 @@ __global__ void k_cg_advance(int chunk, int shift, Slot* slots, SolveState* st, 
     return;
   }
   slots[shift] = slots[chunk + shift];
+  slots[shift].pad = 1;  // a rolled-over record: its update belongs to the chunk before (amg.hip px_records)
   st->base += chunk;
 }
 
