@@ -117,6 +117,47 @@ int mfea_destroy(mfea_handle* h);
 /* Material constants, src/fea_solver.py:14-20 / src/fea_petsc.cpp:23-27. */
 int mfea_set_material(mfea_handle* h, double E, double A, double I);
 
+/* ---- per-element section, modulus and failure strain ----------------------- */
+/* A heterogeneous network: each column is an array of n_elems doubles indexed
+ * by the element's row in the mesh (elements.csv), or NULL for the handle's
+ * scalar (E, A, I of mfea_set_material) / the call's scalar (max_strain of
+ * mfea_post, mfea_step, mfea_run, mfea_event_opts).  The library copies the
+ * arrays.  NULL, or every column NULL: back to the uniform engine.
+ *   assembly  k_ax = (E_e·A_e)/L_safe, k_b = ((12·E_e)·I_e)/L_safe³ — the host
+ *             forms EA_e = E_e*A_e and EI12_e = (12.0*E_e)*I_e with the
+ *             expressions and rounding of mfea_set_material;
+ *   post      stress_e = E_e·ε_e; element e fails when |ε_e| > max_strain_e
+ *             (+inf: never);
+ *   events    see mfea_event.
+ * Call order: after mfea_set_mesh (MFEA_ESTATE before it).  mfea_set_mesh
+ * clears the properties; mfea_set_bc, mfea_set_active and mfea_set_material
+ * keep them — a later mfea_set_material changes only the columns given as NULL.
+ * MFEA_EINVAL, the handle unchanged, unless every E, A, I is finite and >= 0
+ * and every max_strain is > 0 and not NaN (+inf allowed).
+ * One partition only: MFEA_ESTATE on a partitioned handle (mfea_debug_set_parts,
+ * an RCCL world); a handle with properties that is partitioned afterwards
+ * returns MFEA_ESTATE from its next build.
+ * A change drops everything option "keep_operator" keeps (K, the GAMG
+ * hierarchy's values) and every captured graph that holds the old properties;
+ * the symbolic hierarchy stays (amg_rebuilt == 0): the active set did not move.
+ * With "amg_theta_ppm" > 0 the strength estimate weighs each coupling by its
+ * element's own EA_e and EI12_e/EA_e.
+ * The uniform identity: arrays filled with the handle's scalars and the call's
+ * max_strain give K, U, iteration counts, force, stress, activity and n_active
+ * bit for bit those of the uniform engine, for every preconditioner (θ = 0).
+ * mfea_element_stiffness stays uniform. */
+typedef struct {
+  const double* E;          /* n_elems, or NULL: the handle's E (mfea_set_material)            */
+  const double* A;          /* n_elems, or NULL: the handle's A                                */
+  const double* I;          /* n_elems, or NULL: the handle's I                                */
+  const double* max_strain; /* n_elems, or NULL: the call's scalar; > 0, +inf = never fails    */
+} mfea_element_props;
+int mfea_set_element_props(mfea_handle* h, const mfea_element_props* p);
+/* What the engine uses, n_elems doubles per non-NULL argument: a column that
+ * was not set comes back filled with the handle's scalar — max_strain with
+ * NaN, because that scalar belongs to the call, not to the handle. */
+int mfea_get_element_props(mfea_handle* h, double* E, double* A, double* I, double* max_strain);
+
 /* ---- mesh + boundary conditions (symbolic, once per mesh) ------------------ */
 /* Replaces the CSV→array hand-off of fea_solver (src/fea_solver.py:193-201) and
  * read_nodes_csv/read_elems_csv (src/fea_petsc.cpp:42-82, 179-200).
@@ -153,7 +194,10 @@ int mfea_solve(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_op
 /* Reaction + stress/failure on device.  Replaces src/fea_solver.py:256-284 and
  * src/fea_petsc.cpp:360-406: total_force = Σ_{top} (K·U)[3n+1] on the
  * unregularised K; stress = E·ε for elements active at step start (0 else);
- * elements with |ε| > max_strain are deactivated for the next step. */
+ * elements with |ε| > max_strain are deactivated for the next step.
+ * With per-element properties (mfea_set_element_props): stress_e = E_e·ε_e and
+ * element e fails when |ε_e| > max_strain_e; with a strength array the scalar
+ * max_strain is otherwise unused (here, in mfea_step and in mfea_run). */
 int mfea_post(mfea_handle* h, double max_strain, double* total_force, int64_t* n_active);
 /* One full load step = assemble + solve + post (the bench "step").
  * On a handle with one partition the step keeps what the grip displacements
@@ -256,7 +300,24 @@ int mfea_run(mfea_handle* h, int32_t n_steps, const double* dy_top, const double
  * "keep_operator" keeps nothing from one breaking event to the next — each
  * changes the active set — but the symbolic hierarchy is kept as for steps.
  * MFEA_EINVAL unless max_strain > 0, 0 <= tie_rtol < 1, lam_max > 0 (+inf
- * allowed); one partition only (MFEA_ESTATE otherwise, as mfea_run). */
+ * allowed); one partition only (MFEA_ESTATE otherwise, as mfea_run).
+ * With a per-element strength (mfea_set_element_props, max_strain), each of the
+ * following one IEEE operation:
+ *   lam_e  max_strain_e / |ε_e| over the active, valid elements with |ε_e| > 0
+ *          (NaN strains skipped as above);
+ *   lam    min_e lam_e, +inf when there is none or every such strength is +inf
+ *          (the unloaded terminal event, MFEA_EVENTS_UNLOADED in a run);
+ *   if lam <= lam_max (and lam < +inf), every such element with
+ *          lam_e <= lam / (1 − tie_rtol) fails (difference and quotient rounded
+ *          once each);
+ *   stress (E_e·ε_e)·factor, the factor as above.
+ * evopts->max_strain is still validated and otherwise unused.  Without a
+ * strength array the smax rule above runs unchanged, with E_e in the stress
+ * row when E is per element.  On arrays filled with the scalar, lam is bit for
+ * bit the uniform one (a correctly rounded division is monotone:
+ * min_e fl(m/|ε_e|) = fl(m/max_e |ε_e|)); the failing group can differ from
+ * |ε_e| >= smax·(1 − tie_rtol) only for an element within rounding of that
+ * boundary. */
 typedef struct {
   double max_strain; /* failure strain, src/fea_solver.py:20 MAX_STRAIN                      */
   double tie_rtol;   /* relative width of the failing group below smax (1e-9 is a good default) */

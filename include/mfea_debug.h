@@ -156,7 +156,8 @@ int mfea_debug_floating(mfea_handle* h, uint8_t* out);
  *                        chunk of a planned batch that is not one graph of its own length
  *                        (8; 2..63).  Keeps K and the hierarchy's values when set.
  * Read-only: "sweep_colors", "sweep_pieces" (the last SOR / ICC plan), "asm_colours"
- * (the element colouring's colours once asm_kernel 1 or 2 has run; 0 before).
+ * (the element colouring's colours once asm_kernel 1 or 2 has run; 0 before),
+ * "element_props" (1 while mfea_set_element_props holds any per-element column, else 0).
  * Options that change the symbolic layout rebuild it at the next call. */
 int mfea_set_option(mfea_handle* h, const char* name, int64_t value);
 

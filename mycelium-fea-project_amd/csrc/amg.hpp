@@ -153,6 +153,11 @@ struct AmgDistSpec {
 struct AmgStrength {
   double theta = 0.0;
   double kb_kax = 0.0;
+  // per-element sections (mfea_set_element_props): (EA_e, EI12_e) pairs by
+  // element id, or NULL.  Then ‖S_e‖ = EA_e/L · √(1 + ((EI12_e/EA_e)/L²)²):
+  // the element's own weight in place of the constant (which cancels in the
+  // uniform test, so it is left out there)
+  const double* sec = nullptr;
 };
 
 // Row labels of the device layout (stage 2 of the symbolic phase).  The

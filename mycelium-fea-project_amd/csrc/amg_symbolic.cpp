@@ -462,13 +462,19 @@ std::string build_amg(const Pattern& P, const std::vector<uint8_t>& active, int 
   // per row Σ ‖S_e‖ of every active incident element (its diagonal's estimate)
   const bool use_strength = strength.theta > 0.0;
   std::vector<double> w_entry, d_row;
-  auto enorm = [&](int64_t i, int64_t j) {
+  auto enorm = [&](int64_t i, int64_t j, int32_t e) {
     double v[3], L2 = 0.0;
     for (int c = 0; c < 3; ++c) {
       v[c] = P.xyz_perm[3 * j + c] - P.xyz_perm[3 * i + c];
       L2 += v[c] * v[c];
     }
-    const double L = std::max(std::sqrt(L2), 1e-12), q = strength.kb_kax / (L * L);
+    const double L = std::max(std::sqrt(L2), 1e-12);
+    if (strength.sec) {
+      const double EA = strength.sec[2 * (int64_t)e], EI12 = strength.sec[2 * (int64_t)e + 1];
+      const double q = (EA > 0.0 ? EI12 / EA : 0.0) / (L * L);
+      return EA * std::sqrt(1.0 + q * q) / L;
+    }
+    const double q = strength.kb_kax / (L * L);
     return std::sqrt(1.0 + q * q) / L;
   };
   if (use_strength) {
@@ -479,7 +485,7 @@ std::string build_amg(const Pattern& P, const std::vector<uint8_t>& active, int 
         const int64_t pos = base + (int64_t)t * 64;
         const int32_t j = P.s_col[pos], e = P.s_elem[pos];
         if (j < 0 || e < 0 || !active[e]) continue;
-        d_row[i] += enorm(i, j);
+        d_row[i] += enorm(i, j, e);
       }
     }
   }
@@ -508,7 +514,7 @@ std::string build_amg(const Pattern& P, const std::vector<uint8_t>& active, int 
         if (w) w->push_back(0.0);
       }
       s.item(nb[t].second);
-      if (w) w->back() += enorm(i, nb[t].first);
+      if (w) w->back() += enorm(i, nb[t].first, P.s_elem[nb[t].second]);
     }
   };
   if (!use_strength) {

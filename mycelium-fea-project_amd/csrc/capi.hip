@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <deque>
+#include <limits>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -238,11 +239,38 @@ struct Part {
   bool rec_ok = false;
 };
 
+// What the assembly and post kernels take their material from: the scalars by
+// value and the generation of the per-element properties (their device
+// pointers and the uniform / per-element kernel choice).  Compared and hashed
+// wherever K or a captured graph remembers what it was formed with.
+struct MatKey {
+  Material mat{};
+  int64_t props_gen = 0;
+  bool operator==(const MatKey& o) const {
+    return std::memcmp(&mat, &o.mat, sizeof mat) == 0 && props_gen == o.props_gen;
+  }
+  bool operator!=(const MatKey& o) const { return !(*this == o); }
+};
+
 struct mfea_handle {
   int device = 0;
   hipStream_t stream = nullptr;
   double E = 2500.0, A = 0.0, I = 0.0;
   Material mat{};
+  // mfea_set_element_props (one partition): the columns the caller gave, in
+  // element order (empty: the handle's scalar / the call's max_strain), and
+  // what the kernels read — the interleaved (EA_e, EI12_e) pairs when any of
+  // E, A, I is an array, E_e, max_strain_e.  props_gen: bumped by every change
+  // of them (monotonic; MatKey).
+  std::vector<double> pe_E, pe_A, pe_I, pe_S;
+  std::vector<double> pe_sec;  // host copy of the pairs (the AMG strength estimate)
+  DevBuf<double> pe_sec_d, pe_E_d, pe_S_d;
+  int64_t props_gen = 0;
+  MatKey mat_key() const { return MatKey{mat, props_gen}; }
+  bool has_props() const { return !pe_E.empty() || !pe_A.empty() || !pe_I.empty() || !pe_S.empty(); }
+  const double2* sec_d() const { return pe_sec.empty() ? nullptr : reinterpret_cast<const double2*>(pe_sec_d.ptr); }
+  const double* Ee_d() const { return pe_E.empty() ? nullptr : pe_E_d.ptr; }
+  const double* strength_d() const { return pe_S.empty() ? nullptr : pe_S_d.ptr; }
   // host-side mesh/BC (original order)
   int64_t N = 0, Ecount = 0;
   std::vector<double> xyz;
@@ -337,7 +365,7 @@ struct mfea_handle {
   struct {
     bool ok = false;
     int64_t act_gen = -1;
-    Material mat{};
+    MatKey mat{};
     int asm_kernel = -1;
   } k_from;
   int last_precond = -1;          // the last solve's preconditioner kind
@@ -359,7 +387,7 @@ struct mfea_handle {
   int opt_amg_lazy_px = 1;
   int64_t amg_px_replays = 0;     // read-only option: replay launches queued by the solves
   bool setup_skipped = false;     // the last solve did (phase times: t_setup_ms = 0)
-  Material graph_batch_mat{};     // the material graph_batch's post kernels were captured with
+  MatKey graph_batch_mat{};       // the material / properties graph_batch's post kernels were captured with
   bool asm_pending = false;  // mfea_step deferred its assembly to solve_amg
   DevBuf<double> d_dy;
   bool spec_on = false;
@@ -521,17 +549,35 @@ void drop_kept(mfea_handle* h) {
   h->k_from.ok = false;
   drop_kept_setup(h);
 }
+// The per-element properties changed (or went): K, the hierarchies' values and
+// every captured graph that holds a property pointer or a kernel's uniform /
+// per-element form are the old ones' (MatKey) — the symbolic hierarchy stays,
+// the active set did not move
+void props_changed(mfea_handle* h) {
+  ++h->props_gen;
+  ++h->op_gen;
+  drop_kept(h);
+}
+void clear_props(mfea_handle* h) {
+  if (!h->has_props()) return;
+  h->pe_E.clear();
+  h->pe_A.clear();
+  h->pe_I.clear();
+  h->pe_S.clear();
+  h->pe_sec.clear();
+  props_changed(h);
+}
 // K (val / diag) is what an assembly would write now
 bool k_current(const mfea_handle* h) {
   return h->opt_keep_operator && h->assembled && h->k_from.ok && h->k_from.act_gen == h->act_gen &&
-         std::memcmp(&h->k_from.mat, &h->mat, sizeof h->mat) == 0 && h->k_from.asm_kernel == h->opt_asm_kernel;
+         h->k_from.mat == h->mat_key() && h->k_from.asm_kernel == h->opt_asm_kernel;
 }
 // ... recorded by every launch that writes them
 void k_written(mfea_handle* h) {
   ++h->op_gen;
   h->k_from.ok = true;
   h->k_from.act_gen = h->act_gen;
-  h->k_from.mat = h->mat;
+  h->k_from.mat = h->mat_key();
   h->k_from.asm_kernel = h->opt_asm_kernel;
 }
 
@@ -549,6 +595,39 @@ hipError_t hmemcpy(mfea_handle* h, void* dst, const void* src, size_t n, hipMemc
 hipError_t hmemset(mfea_handle* h, void* dst, int v, size_t n) {
   const hipError_t e = hipMemsetAsync(dst, v, n, h->stream);
   return e == hipSuccess ? hipStreamSynchronize(h->stream) : e;
+}
+
+// The device form of the per-element properties from the host columns and the
+// handle's scalars: EA_e = E_e*A_e and EI12_e = (12.0*E_e)*I_e, the expressions
+// and rounding of mfea_set_material.  The stream is drained first (a kernel of
+// an earlier call may still read the arrays) and after.
+int upload_props(mfea_handle* h) {
+  const int64_t n = h->Ecount;
+  props_changed(h);
+  h->pe_sec.clear();
+  if (!h->has_props() || n <= 0) return 0;
+  HIPC(hipStreamSynchronize(h->stream));
+  if (!h->pe_E.empty() || !h->pe_A.empty() || !h->pe_I.empty()) {
+    h->pe_sec.resize(2 * n);
+    for (int64_t e = 0; e < n; ++e) {
+      const double E = h->pe_E.empty() ? h->E : h->pe_E[e];
+      const double A = h->pe_A.empty() ? h->A : h->pe_A[e];
+      const double I = h->pe_I.empty() ? h->I : h->pe_I[e];
+      h->pe_sec[2 * e] = E * A;
+      h->pe_sec[2 * e + 1] = (12.0 * E) * I;
+    }
+    HIPC(h->pe_sec_d.alloc(2 * n));
+    HIPC(hmemcpy(h, h->pe_sec_d.ptr, h->pe_sec.data(), 2 * n * sizeof(double), hipMemcpyHostToDevice));
+  }
+  if (!h->pe_E.empty()) {
+    HIPC(h->pe_E_d.alloc(n));
+    HIPC(hmemcpy(h, h->pe_E_d.ptr, h->pe_E.data(), n * sizeof(double), hipMemcpyHostToDevice));
+  }
+  if (!h->pe_S.empty()) {
+    HIPC(h->pe_S_d.alloc(n));
+    HIPC(hmemcpy(h, h->pe_S_d.ptr, h->pe_S.data(), n * sizeof(double), hipMemcpyHostToDevice));
+  }
+  return 0;
 }
 
 double* cg_part_buf(Part& pt, int par) { return pt.cg_part.ptr + (size_t)par * 4 * kCgMaxPartials; }
@@ -784,6 +863,8 @@ int ensure_built(mfea_handle* h) {
   h->assembled = false;
   h->gkey_gen = -1;
   const bool dm = h->world > 1 || h->nparts > 1;
+  if (dm && h->has_props())
+    return fail(MFEA_ESTATE, "per-element properties: one partition per handle (mfea_set_element_props(h, NULL) first)");
   const int np = h->world > 1 ? 1 : h->nparts;
   const bool skip = (h->mesh_flags & MFEA_MESH_SKIP_INVALID) != 0;
   h->parts.clear();
@@ -1405,6 +1486,7 @@ AmgStrength amg_strength(const mfea_handle* h) {
   AmgStrength st;
   st.theta = h->opt_amg_theta_ppm * 1e-6;
   st.kb_kax = h->mat.EA > 0.0 ? h->mat.EI12 / h->mat.EA : 0.0;
+  st.sec = h->pe_sec.empty() ? nullptr : h->pe_sec.data();  // (one partition: element ids are the pattern's)
   return st;
 }
 
@@ -2286,7 +2368,7 @@ void enqueue_step_head(mfea_handle* h, Part& pt, const mfea_solve_opts* o) {
   q.ticket = tix(pt, 0);
   q.red_out = pt.red.ptr;
   launch_assemble(s, P.n_nodes, pt.xyz_d.ptr, pt.slice_ptr.ptr, pt.row_len.ptr, pt.s_col.ptr, pt.s_elem.ptr,
-                  pt.active.ptr, h->mat, pt.G, pt.val.ptr, pt.diag.ptr, &q);
+                  pt.active.ptr, h->mat, pt.G, pt.val.ptr, pt.diag.ptr, &q, h->sec_d());
   launch_cg_init_finalize(s, pt.red.ptr, o->rtol, o->atol, o->norm, o->max_it, o->reg, pt.state.ptr,
                           pt.cg_part.ptr, 2 * 4 * kCgMaxPartials);
 }
@@ -2354,6 +2436,7 @@ int launch_amg_setup_graph(mfea_handle* h, Part& pt, double reg, uint64_t k0, bo
     k = fnv1a(k, hd, sizeof hd);
     k = fnv1a(k, hi, sizeof hi);
     k = fnv1a(k, &h->mat, sizeof h->mat);
+    k = fnv1a(k, &h->props_gen, sizeof h->props_gen);  // (the section pairs' pointer, the kernel's form)
     k = fnv1a(k, &pt.tickets.ptr, sizeof pt.tickets.ptr);
   }
   if (tail >= 0) {
@@ -2364,6 +2447,7 @@ int launch_amg_setup_graph(mfea_handle* h, Part& pt, double reg, uint64_t k0, bo
     k = fnv1a(k, &tag, sizeof tag);
     k = fnv1a(k, &h->spec_strain, sizeof h->spec_strain);
     k = fnv1a(k, &h->mat, sizeof h->mat);  // (the post's stress kernel holds it by value)
+    k = fnv1a(k, &h->props_gen, sizeof h->props_gen);  // (... and the property pointers, in its form for them)
     hipGraphExec_t& gc = h->graph_combo[form][tail];
     if (!gc || h->graph_combo_key[form][tail] != k) {
       if (gc) {
@@ -2607,14 +2691,14 @@ int solve_amg(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opt
     // (batch_graph: C2 / C3 two graph launches and four eager ones fewer per step)
     if (batch) {
       if (h->graph_batch_ell != tag || h->graph_batch_strain != h->spec_strain ||
-          std::memcmp(&h->graph_batch_mat, &h->mat, sizeof h->mat) != 0) {
+          h->graph_batch_mat != h->mat_key()) {
         for (auto& g : h->graph_batch) {
           if (g) (void)hipGraphExecDestroy(g);
           g = nullptr;
         }
         h->graph_batch_ell = tag;
         h->graph_batch_strain = h->spec_strain;
-        h->graph_batch_mat = h->mat;  // (the post's stress kernel holds it by value)
+        h->graph_batch_mat = h->mat_key();  // (the post's stress kernel holds them by value)
       }
       if (!combo && h->graph_batch[need] == nullptr) {
         hipGraph_t g;
@@ -3439,12 +3523,12 @@ int assemble_impl(mfea_handle* h, mfea_stats* st, const double* rhs_dy = nullptr
     const Pattern& P = pt.P;
     if (h->opt_asm_kernel == 1 && ensure_colour(h, pt)) {
       launch_assemble_colour(s, pt.ec.colors, pt.ec.cstart.data(), pt.ec_entry.ptr, pt.e2n_d.ptr, pt.ec_pos.ptr,
-                             pt.xyz_d.ptr, pt.active.ptr, h->mat, pt.G, P.n_nodes, pt.val.ptr, pt.diag.ptr);
+                             pt.xyz_d.ptr, pt.active.ptr, h->mat, pt.G, P.n_nodes, pt.val.ptr, pt.diag.ptr, h->sec_d());
       continue;  // (RHS: its own kernel in the solve, rhs_fused stays false)
     }
     if (h->opt_asm_kernel == 2 && ensure_colour(h, pt)) {
       launch_assemble_elems(s, P.n_elems, P.n_nodes, pt.e2n_d.ptr, pt.ec_pos.ptr, pt.xyz_d.ptr, pt.active.ptr,
-                            h->mat, pt.slice_ptr.ptr, pt.row_len.ptr, pt.G, pt.val.ptr, pt.diag.ptr);
+                            h->mat, pt.slice_ptr.ptr, pt.row_len.ptr, pt.G, pt.val.ptr, pt.diag.ptr, h->sec_d());
       continue;
     }
     AsmRhs q{};
@@ -3466,7 +3550,8 @@ int assemble_impl(mfea_handle* h, mfea_stats* st, const double* rhs_dy = nullptr
       h->rhs_dy[1] = rhs_dy[1];
     }
     launch_assemble(s, P.n_nodes, pt.xyz_d.ptr, pt.slice_ptr.ptr, pt.row_len.ptr, pt.s_col.ptr,
-                    pt.s_elem.ptr, pt.active.ptr, h->mat, pt.G, pt.val.ptr, pt.diag.ptr, rhs ? &q : nullptr);
+                    pt.s_elem.ptr, pt.active.ptr, h->mat, pt.G, pt.val.ptr, pt.diag.ptr, rhs ? &q : nullptr,
+                    h->sec_d());
   }
   HIPC(hipGetLastError());
   RC(phase_event(h, h->ev[1], s));
@@ -3580,7 +3665,8 @@ int enqueue_post_work(mfea_handle* h, double max_strain) {
     // last failures were read (local_failures)
     launch_stress(s, P.n_elems, pt.e2n_d.ptr, pt.xyz_d.ptr, pt.x.ptr, h->mat, max_strain,
                   pt.active.ptr, pt.stress.ptr, pt.partials.ptr, tix(pt, 4), pt.red.ptr + 5,
-                  dm ? pt.elem_own.ptr : nullptr, pt.fail_list.ptr, dm ? pt.fail_cnt.ptr : fail_counter(pt));
+                  dm ? pt.elem_own.ptr : nullptr, pt.fail_list.ptr, dm ? pt.fail_cnt.ptr : fail_counter(pt),
+                  h->Ee_d(), h->strength_d());
   }
   HIPC(hipGetLastError());
   Part& p0 = part0(h);
@@ -3628,6 +3714,7 @@ int enqueue_event_work(mfea_handle* h) {
   q.ticket_e = tix(pt, 4);
   q.cnt_out = pt.red.ptr + 5;
   q.smax_out = pt.red.ptr + 7;
+  q.strength = h->strength_d();
   launch_event_scan(s, q);
   EventApply a{};
   a.E = P.n_elems;
@@ -3650,6 +3737,8 @@ int enqueue_event_work(mfea_handle* h) {
   a.ticket = tix(pt, 4);
   a.cnt_out = pt.red.ptr + 5;
   a.lam_out = pt.red.ptr + 8;
+  a.Ee = h->Ee_d();
+  a.strength = h->strength_d();
   launch_event_apply(s, a);
   HIPC(hipGetLastError());
   HIPC(hipMemcpyAsync(h->h_red, pt.red.ptr + 4, 5 * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -3900,6 +3989,58 @@ int mfea_set_material(mfea_handle* h, double E, double A, double I) {
   // graphs that hold the material by value are keyed by it (graph_batch_mat,
   // the combined graph's key)
   ++h->op_gen;
+  // per-element columns stay; the columns left to the scalars follow them
+  if (h->has_props()) {
+    RC(set_device(h));
+    RC(upload_props(h));
+  }
+  return 0;
+}
+
+static bool props_column_ok(const double* v, int64_t n, bool strength) {
+  for (int64_t e = 0; v && e < n; ++e) {
+    if (strength ? !(v[e] > 0.0) : !(std::isfinite(v[e]) && v[e] >= 0.0)) return false;
+  }
+  return true;
+}
+
+int mfea_set_element_props(mfea_handle* h, const mfea_element_props* p) {
+  if (!h) return fail(MFEA_EINVAL, "NULL handle");
+  if (!h->has_mesh) return fail(MFEA_ESTATE, "set the mesh before the element properties");
+  if (h->world > 1 || h->nparts > 1 || h->parts.size() > 1)
+    return fail(MFEA_ESTATE, "mfea_set_element_props: one partition per handle");
+  const int64_t n = h->Ecount;
+  const mfea_element_props none{nullptr, nullptr, nullptr, nullptr};
+  if (!p) p = &none;
+  if (!props_column_ok(p->E, n, false) || !props_column_ok(p->A, n, false) || !props_column_ok(p->I, n, false))
+    return fail(MFEA_EINVAL, "mfea_set_element_props: E, A, I must be finite and >= 0");
+  if (!props_column_ok(p->max_strain, n, true))
+    return fail(MFEA_EINVAL, "mfea_set_element_props: max_strain must be > 0 (+inf allowed)");
+  RC(set_device(h));
+  auto take = [n](std::vector<double>& v, const double* src) {
+    if (src && n > 0) v.assign(src, src + n);
+    else v.clear();
+  };
+  take(h->pe_E, p->E);
+  take(h->pe_A, p->A);
+  take(h->pe_I, p->I);
+  take(h->pe_S, p->max_strain);
+  return upload_props(h);
+}
+
+int mfea_get_element_props(mfea_handle* h, double* E, double* A, double* I, double* max_strain) {
+  if (!h) return fail(MFEA_EINVAL, "NULL handle");
+  if (!h->has_mesh) return fail(MFEA_ESTATE, "no mesh: call mfea_set_mesh first");
+  const int64_t n = h->Ecount;
+  auto give = [n](double* out, const std::vector<double>& v, double scalar) {
+    if (!out) return;
+    if (v.empty()) std::fill(out, out + n, scalar);
+    else std::copy(v.begin(), v.end(), out);
+  };
+  give(E, h->pe_E, h->E);
+  give(A, h->pe_A, h->A);
+  give(I, h->pe_I, h->I);
+  give(max_strain, h->pe_S, std::numeric_limits<double>::quiet_NaN());
   return 0;
 }
 
@@ -3918,6 +4059,7 @@ int mfea_set_mesh(mfea_handle* h, int64_t n_nodes, const double* xyz, int64_t n_
   h->dirty = true;
   h->act_all = false;
   h->active_host.clear();
+  clear_props(h);  // (indexed by the old mesh's elements)
   h->planar = true;
   for (int64_t n = 0; n < n_nodes; ++n)
     if (xyz[3 * n + 2] != 0.0) h->planar = false;
@@ -4475,7 +4617,9 @@ int mfea_run_events(mfea_handle* h, int32_t n_events, double dy_top, double dy_b
       if (rc) break;
       *n_done = k + 1;
       if (out.n_failed == 0) {  // terminal: smax = 0 (unloaded) or lam > lam_max
-        *stop_reason = h->h_red[3] > 0.0 ? MFEA_EVENTS_LAMBDA_MAX : MFEA_EVENTS_UNLOADED;
+        // (with a per-element strength h_red[3] is the scan's lam: +inf when unloaded)
+        const bool loaded = h->pe_S.empty() ? h->h_red[3] > 0.0 : std::isfinite(h->h_red[3]);
+        *stop_reason = loaded ? MFEA_EVENTS_LAMBDA_MAX : MFEA_EVENTS_UNLOADED;
         break;
       }
     }
@@ -5209,6 +5353,7 @@ int mfea_get_option(mfea_handle* h, const char* name, int64_t* value) {
   if (n == "graph") *value = h->opt_graph;
   else if (n == "run_register") *value = h->opt_run_register ? 1 : 0;
   else if (n == "event_scratch") *value = h->opt_event_scratch;
+  else if (n == "element_props") *value = h->has_props() ? 1 : 0;  // read-only: per-element columns are set
   else if (n == "run_direct") *value = h->run_direct;  // read-only: the last mfea_run's host path
   else if (n == "phase_times") *value = h->opt_phase_times ? 1 : 0;
   else if (n == "dist_graph") *value = h->opt_dist_graph;

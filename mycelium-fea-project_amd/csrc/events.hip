@@ -9,6 +9,12 @@
 //                  at the failure load, #active — reads smax from device
 //                  memory, so no host round trip lies between the two.
 //
+// With a per-element strength (mfea_set_element_props, max_strain) the pair
+// runs in its second form: the scan reduces lam = min_e max_strain_e / |ε_e|
+// (identity +inf) where it reduced smax, and the apply fails every element
+// with lam_e <= lam / (1 − tie_rtol).  Both forms are template instantiations;
+// the uniform one is the code it was.
+//
 // Every expression below is one IEEE f64 operation (the build disables
 // contraction), so NumPy reproduces the results bit for bit.
 #include "kernels.hpp"
@@ -42,16 +48,17 @@ __device__ __forceinline__ double element_strain(const int32_t* __restrict__ e2n
 }
 
 // max over the block, result on thread 0 (a max is order-free: any tree gives
-// the same bits)
+// the same bits); MIN: the min instead (identity +inf), order-free likewise
+template <bool MIN = false>
 __device__ __forceinline__ double block_max(double v, double* lds) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+  for (int o = 32; o > 0; o >>= 1) v = MIN ? fmin(v, __shfl_xor(v, o)) : fmax(v, __shfl_xor(v, o));
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   __syncthreads();
   if (lane == 0) lds[wid] = v;
   __syncthreads();
   if (threadIdx.x == 0)
-    for (int w = 1; w < kBlock / 64; ++w) v = fmax(v, lds[w]);
+    for (int w = 1; w < kBlock / 64; ++w) v = MIN ? fmin(v, lds[w]) : fmax(v, lds[w]);
   return v;
 }
 
@@ -62,7 +69,10 @@ __device__ __forceinline__ double block_max(double v, double* lds) {
 // given), the block's max |ε| over active elements (NaN skipped) and its
 // number of active elements; the block that finishes the count's reduction
 // (every element block has published by then) takes the max of the block maxima.
+// PS (q.strength): lam_e = max_strain_e / |ε_e| of the same elements and the
+// min in place of the max, through the same publish.
 // ---------------------------------------------------------------------------
+template <bool PS>
 __global__ __launch_bounds__(kBlock) void k_event_scan(EventScan q) {
   __shared__ double mx[kBlock / 64];
   if (blockIdx.x < q.grid_r) {
@@ -101,7 +111,7 @@ __global__ __launch_bounds__(kBlock) void k_event_scan(EventScan q) {
   const unsigned be = blockIdx.x - q.grid_r;
   const int64_t e = (int64_t)be * kBlock + threadIdx.x;
   double cnt[1] = {0.0};
-  double m = 0.0;
+  double m = PS ? (double)INFINITY : 0.0;
   if (q.E > 0) {
     const bool in = e < q.E;
     const int64_t ec = in ? e : q.E - 1;
@@ -111,17 +121,23 @@ __global__ __launch_bounds__(kBlock) void k_event_scan(EventScan q) {
     if (q.eps && in) q.eps[e] = strain;
     const double as = fabs(strain);
     // (a NaN strain — a zero-length element — compares false: skipped)
-    if (in && act && valid && as > 0.0) m = as;
+    if constexpr (PS) {
+      const double ms = q.strength[ec];
+      if (in && act && valid && as > 0.0) m = ms / as;
+    } else {
+      if (in && act && valid && as > 0.0) m = as;
+    }
     cnt[0] = (in && act) ? 1.0 : 0.0;
   }
-  m = block_max(m, mx);
+  m = block_max<PS>(m, mx);
   if (threadIdx.x == 0) store_sc1(&q.pmax[be], m);
   // (thread 0 drains its stores — the block maximum among them — before its
   // ticket in block_publish_as)
   if (!block_publish_as<1>(cnt, q.partials_e, q.ticket_e, q.cnt_out, q.grid_e, be)) return;
-  double r = 0.0;
-  for (unsigned k = threadIdx.x; k < q.grid_e; k += kBlock) r = fmax(r, load_sc1(&q.pmax[k]));
-  r = block_max(r, mx);
+  double r = PS ? (double)INFINITY : 0.0;
+  for (unsigned k = threadIdx.x; k < q.grid_e; k += kBlock)
+    r = PS ? fmin(r, load_sc1(&q.pmax[k])) : fmax(r, load_sc1(&q.pmax[k]));
+  r = block_max<PS>(r, mx);
   if (threadIdx.x == 0) *q.smax_out = r;
 }
 
@@ -133,13 +149,18 @@ __global__ __launch_bounds__(kBlock) void k_event_scan(EventScan q) {
 // k_stress.  Otherwise the event is terminal and no activity is touched.
 // stress = (E·ε)·lam for elements active at event start (terminal: the factor
 // is lam_max when finite, else 1), 0 otherwise.  Reduces #active (after).
+// PS (q.strength): *q.smax holds the scan's lam = min lam_e (+inf: no loaded
+// element of finite strength — terminal); the group is every active, valid
+// element with |ε| > 0 and lam_e = max_strain_e / |ε_e| <= lam / (1 − tie_rtol).
+// PM (q.Ee): E_e in the stress row.
 // ---------------------------------------------------------------------------
+template <bool PS, bool PM>
 __global__ __launch_bounds__(kBlock) void k_event_apply(EventApply q) {
   const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   const double smax = *q.smax;
-  const double lam = q.max_strain / smax;
-  const bool breaks = smax > 0.0 && lam <= q.lam_max;
-  const double thr = smax * (1.0 - q.tie_rtol);
+  const double lam = PS ? smax : q.max_strain / smax;
+  const bool breaks = PS ? (lam < (double)INFINITY && lam <= q.lam_max) : (smax > 0.0 && lam <= q.lam_max);
+  const double thr = PS ? lam / (1.0 - q.tie_rtol) : smax * (1.0 - q.tie_rtol);
   const double factor = breaks ? lam : (isfinite(q.lam_max) ? q.lam_max : 1.0);
   if (blockIdx.x == 0 && threadIdx.x == 0) *q.lam_out = lam;
   double cnt[1] = {0.0};
@@ -155,10 +176,14 @@ __global__ __launch_bounds__(kBlock) void k_event_apply(EventApply q) {
     } else {
       strain = element_strain(q.e2n, q.xyz, q.u, ec, &valid);
     }
+    double Em = q.Emod, ms = 0.0;
+    if constexpr (PM) Em = q.Ee[ec];
+    if constexpr (PS) ms = q.strength[ec];
     if (in) {
       const bool live = act0 && valid;
-      const bool fails = live && breaks && fabs(strain) >= thr;
-      q.stress[e] = live ? (q.Emod * strain) * factor : 0.0;
+      const double as = fabs(strain);
+      const bool fails = PS ? (live && breaks && as > 0.0 && ms / as <= thr) : (live && breaks && as >= thr);
+      q.stress[e] = live ? (Em * strain) * factor : 0.0;
       if (fails) {
         q.active[e] = 0;
         q.event_of[e] = q.k;
@@ -193,7 +218,8 @@ void launch_event_scan(hipStream_t s, EventScan q) {
   q.partials_r = q.partials;
   q.partials_e = q.partials_r + (q.grid_r + kShards);
   q.pmax = q.partials_e + (q.grid_e + kShards);
-  hipLaunchKernelGGL(k_event_scan, dim3(q.grid_r + q.grid_e), dim3(kBlock), 0, s, q);
+  if (q.strength) hipLaunchKernelGGL(k_event_scan<true>, dim3(q.grid_r + q.grid_e), dim3(kBlock), 0, s, q);
+  else hipLaunchKernelGGL(k_event_scan<false>, dim3(q.grid_r + q.grid_e), dim3(kBlock), 0, s, q);
 }
 
 int64_t event_scan_partials(int64_t n_top, int64_t n_elems) {
@@ -201,7 +227,10 @@ int64_t event_scan_partials(int64_t n_top, int64_t n_elems) {
 }
 
 void launch_event_apply(hipStream_t s, const EventApply& q) {
-  hipLaunchKernelGGL(k_event_apply, dim3((unsigned)grid_rows(q.E > 0 ? q.E : 1)), dim3(kBlock), 0, s, q);
+  const dim3 g((unsigned)grid_rows(q.E > 0 ? q.E : 1));
+  auto k = q.strength ? (q.Ee ? k_event_apply<true, true> : k_event_apply<true, false>)
+                      : (q.Ee ? k_event_apply<false, true> : k_event_apply<false, false>);
+  hipLaunchKernelGGL(k, g, dim3(kBlock), 0, s, q);
 }
 
 void launch_event_unfail(hipStream_t s, const int32_t* fail_list, unsigned* cnt, uint8_t* active,

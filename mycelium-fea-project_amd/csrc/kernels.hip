@@ -10,6 +10,8 @@
 
 #include <math.h>
 
+#include <type_traits>
+
 namespace mfea {
 
 // ---------------------------------------------------------------------------
@@ -37,13 +39,17 @@ __device__ __forceinline__ double cube(double a) {
   return c + (ec + es * a);
 }
 
-__device__ __forceinline__ void bar_block(double vx, double vy, double vz, const Material& m,
+// the section (EA, EI12) of element e: the handle's, or the element's own pair
+__device__ __forceinline__ double2 section_of(const Material& m, int64_t) { return make_double2(m.EA, m.EI12); }
+__device__ __forceinline__ double2 section_of(const ElemSection& m, int64_t e) { return m.sec[e]; }
+
+__device__ __forceinline__ void bar_block(double vx, double vy, double vz, double EA, double EI12,
                                           double S[6], double* Lout) {
   const double L = sqrt(vx * vx + vy * vy + vz * vz);
   const double Ls = L < 1e-12 ? 1e-12 : L;
   const double n0 = vx / Ls, n1 = vy / Ls, n2 = vz / Ls;
-  const double kax = m.EA / Ls;
-  const double kb = m.EI12 / cube(Ls);
+  const double kax = EA / Ls;
+  const double kb = EI12 / cube(Ls);
   const double t00 = n0 * n0, t01 = n0 * n1, t02 = n0 * n2, t11 = n1 * n1, t12 = n1 * n2,
                t22 = n2 * n2;
   S[0] = t00 * kax + (1.0 - t00) * kb;
@@ -66,14 +72,20 @@ __device__ __forceinline__ void bar_block(double vx, double vy, double vz, const
 // One node row of the assembly; q (a free row of the GAMG solves): also
 // K_fk x_k into k3 — k_amg_rhs's sum of the stored −S_e terms in slot order,
 // the same bits.
+// M: Material (one section for every element) or ElemSection (per-element
+// (EA_e, EI12_e) pairs, kernels.hpp) — a template, not a run-time choice: a
+// selected load would serialise the batch's gathers (below), and the uniform
+// instantiation is the code it was before the pairs existed.
+template <class M>
 __device__ __forceinline__ void assemble_row(int64_t N, int64_t row, const double* __restrict__ xyz,
                                              const int32_t* __restrict__ slice_ptr,
                                              const int32_t* __restrict__ row_len,
                                              const int32_t* __restrict__ s_col,
                                              const int32_t* __restrict__ s_elem,
-                                             const uint8_t* __restrict__ active, const Material& m,
+                                             const uint8_t* __restrict__ active, const M& m,
                                              int64_t G, double* __restrict__ val, double* __restrict__ diag,
                                              const AsmRhs* q, double* k3) {
+  constexpr bool PE = !std::is_same<M, Material>::value;
   const bool rhs = q != nullptr && row < q->nf;
   const int64_t base = (int64_t)slice_ptr[row >> 6] * 64 + (row & 63);
   const int len = row_len[row];
@@ -103,8 +115,14 @@ __device__ __forceinline__ void assemble_row(int64_t N, int64_t row, const doubl
     }
     uint8_t act[U], cd[U];
     double pj[U][3];
+    // per-element section: the slot's (EA_e, EI12_e) pair, one 16-byte load by
+    // the element id the batch already holds — issued in this second group
+    // with the activity and the coordinates, so the batch still waits for two
+    // dependent round trips, not three
+    double2 se[PE ? U : 1];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
+      if constexpr (PE) se[u] = section_of(m, e[u]);
       const uint8_t av = active[e[u]];
       act[u] = ok[u] ? av : 0;
       // the neighbour's class from its row position (no load: a select on a
@@ -120,7 +138,8 @@ __device__ __forceinline__ void assemble_row(int64_t N, int64_t row, const doubl
       if (act[u]) {
         // v = p2 − p1 with the row as either endpoint: the sign of v does not
         // change any product n_a n_b, so S is bitwise endpoint-symmetric.
-        bar_block(pj[u][0] - xi, pj[u][1] - yi, pj[u][2] - zi, m, S, nullptr);
+        if constexpr (PE) bar_block(pj[u][0] - xi, pj[u][1] - yi, pj[u][2] - zi, se[u].x, se[u].y, S, nullptr);
+        else bar_block(pj[u][0] - xi, pj[u][1] - yi, pj[u][2] - zi, m.EA, m.EI12, S, nullptr);
 #pragma unroll
         for (int c = 0; c < 6; ++c) d[c] += S[c];
       }
@@ -155,11 +174,12 @@ __device__ __forceinline__ void assemble_row(int64_t N, int64_t row, const doubl
 // colour order instead of slot order (within a few ulps).  diag is zeroed
 // before the first colour.
 // ---------------------------------------------------------------------------
+template <class M>
 __global__ __launch_bounds__(kBlock) void k_assemble_colour(int64_t e0, int64_t e1, const int32_t* __restrict__ entry,
                                                             const int32_t* __restrict__ e2n,
                                                             const int32_t* __restrict__ epos,
                                                             const double* __restrict__ xyz,
-                                                            const uint8_t* __restrict__ active, Material m,
+                                                            const uint8_t* __restrict__ active, M m,
                                                             int64_t G, int64_t N, double* __restrict__ val,
                                                             double* __restrict__ diag) {
   const int64_t k = e0 + (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -169,9 +189,11 @@ __global__ __launch_bounds__(kBlock) void k_assemble_colour(int64_t e0, int64_t 
   const int32_t a = e2n[2 * e], b = e2n[2 * e + 1];
   const int32_t pa = epos[2 * e], pb = epos[2 * e + 1];
   double S[6] = {0, 0, 0, 0, 0, 0};
-  if (active[e])
+  if (active[e]) {
+    const double2 se = section_of(m, e);
     bar_block(xyz[3 * (int64_t)b] - xyz[3 * (int64_t)a], xyz[3 * (int64_t)b + 1] - xyz[3 * (int64_t)a + 1],
-              xyz[3 * (int64_t)b + 2] - xyz[3 * (int64_t)a + 2], m, S, nullptr);
+              xyz[3 * (int64_t)b + 2] - xyz[3 * (int64_t)a + 2], se.x, se.y, S, nullptr);
+  }
 #pragma unroll
   for (int c = 0; c < 6; ++c) {
     val[(int64_t)c * G + pa] = -S[c];
@@ -195,10 +217,11 @@ __global__ __launch_bounds__(kBlock) void k_assemble_colour(int64_t e0, int64_t 
 // share a slot: no conflicts, no colours, one launch); then one lane per row
 // sums −val over its slots in slot order into the diagonal block — the row
 // gather's own order, so K is bit for bit the row gather's.
+template <class M>
 __global__ __launch_bounds__(kBlock) void k_assemble_elems(int64_t E, const int32_t* __restrict__ e2n,
                                                            const int32_t* __restrict__ epos,
                                                            const double* __restrict__ xyz,
-                                                           const uint8_t* __restrict__ active, Material m,
+                                                           const uint8_t* __restrict__ active, M m,
                                                            int64_t G, double* __restrict__ val) {
   const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (e >= E) return;
@@ -206,9 +229,11 @@ __global__ __launch_bounds__(kBlock) void k_assemble_elems(int64_t E, const int3
   if (pa < 0) return;
   const int32_t a = e2n[2 * e], b = e2n[2 * e + 1];
   double S[6] = {0, 0, 0, 0, 0, 0};
-  if (active[e])
+  if (active[e]) {
+    const double2 se = section_of(m, e);
     bar_block(xyz[3 * (int64_t)b] - xyz[3 * (int64_t)a], xyz[3 * (int64_t)b + 1] - xyz[3 * (int64_t)a + 1],
-              xyz[3 * (int64_t)b + 2] - xyz[3 * (int64_t)a + 2], m, S, nullptr);
+              xyz[3 * (int64_t)b + 2] - xyz[3 * (int64_t)a + 2], se.x, se.y, S, nullptr);
+  }
 #pragma unroll
   for (int c = 0; c < 6; ++c) {
     val[(int64_t)c * G + pa] = -S[c];
@@ -234,14 +259,14 @@ __global__ __launch_bounds__(kBlock) void k_diag_rows(int64_t N, const int32_t* 
 
 // RHS: the GAMG solves' RHS too (AsmRhs: k_amg_rhs's outputs from the −S_e
 // blocks in registers) — one launch fewer per step
-template <bool RHS>
+template <bool RHS, class M>
 __global__ __launch_bounds__(kBlock) void k_assemble(int64_t N, const double* __restrict__ xyz,
                                                      const int32_t* __restrict__ slice_ptr,
                                                      const int32_t* __restrict__ row_len,
                                                      const int32_t* __restrict__ s_col,
                                                      const int32_t* __restrict__ s_elem,
                                                      const uint8_t* __restrict__ active,
-                                                     Material m, int64_t G, double* __restrict__ val,
+                                                     M m, int64_t G, double* __restrict__ val,
                                                      double* __restrict__ diag, AsmRhs q) {
   const int64_t row = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if constexpr (RHS) {
@@ -573,9 +598,19 @@ __global__ __launch_bounds__(kBlock) void k_reaction(int64_t row0, int64_t nrows
 // as BLAS ddot forms it (fma chain x0y0 → +x1y1 → +x2y2), σ = E·ε, deactivate
 // if |ε| > max_strain.  Inactive elements record σ = 0.  Reduces #active.
 // ---------------------------------------------------------------------------
+// M: Material, or ElemPost — E_e and max_strain_e read at e (coalesced), each
+// falling back to the scalar where its array is absent.
+__device__ __forceinline__ double modulus_of(const Material& m, int64_t) { return m.E; }
+__device__ __forceinline__ double modulus_of(const ElemPost& m, int64_t e) { return m.Ee ? m.Ee[e] : m.E; }
+__device__ __forceinline__ double strength_of(const Material&, int64_t, double s) { return s; }
+__device__ __forceinline__ double strength_of(const ElemPost& m, int64_t e, double s) {
+  return m.strength ? m.strength[e] : s;
+}
+
+template <class M>
 __global__ __launch_bounds__(kBlock) void k_stress(int64_t E, const int32_t* __restrict__ e2n,
                                                    const double* __restrict__ xyz,
-                                                   const double* __restrict__ u, Material m,
+                                                   const double* __restrict__ u, M m,
                                                    double max_strain, uint8_t* __restrict__ active,
                                                    double* __restrict__ stress, double* partials,
                                                    unsigned* ticket, double* red_out,
@@ -598,8 +633,8 @@ __global__ __launch_bounds__(kBlock) void k_stress(int64_t E, const int32_t* __r
                    du2 = u[3 * b + 2] - u[3 * a + 2];
       const double dot = fma(n2, du2, fma(n1, du1, n0 * du0));
       const double strain = dot / L;
-      sg = m.E * strain;
-      if (fabs(strain) > max_strain) act = 0;
+      sg = modulus_of(m, e) * strain;
+      if (fabs(strain) > strength_of(m, e, max_strain)) act = 0;
       active[e] = act;
     }
     stress[e] = sg;
@@ -779,8 +814,8 @@ __global__ __launch_bounds__(kBlock) void k_element_stiffness(int64_t n, const d
   const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (e >= n) return;
   double S[6], l;
-  bar_block(p2[3 * e] - p1[3 * e], p2[3 * e + 1] - p1[3 * e + 1], p2[3 * e + 2] - p1[3 * e + 2], m,
-            S, &l);
+  bar_block(p2[3 * e] - p1[3 * e], p2[3 * e + 1] - p1[3 * e + 1], p2[3 * e + 2] - p1[3 * e + 2], m.EA,
+            m.EI12, S, &l);
   L[e] = l;
   const int sidx[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};
   for (int a = 0; a < 6; ++a)
@@ -854,33 +889,50 @@ __global__ __launch_bounds__(kBlock) void k_spmv_csr(int j, int64_t n, const int
 void launch_assemble(hipStream_t s, int64_t N, const double* xyz, const int32_t* slice_ptr,
                      const int32_t* row_len, const int32_t* s_col, const int32_t* s_elem,
                      const uint8_t* active, Material m, int64_t G, double* val, double* diag,
-                     const AsmRhs* rhs) {
+                     const AsmRhs* rhs, const double2* sec) {
+  const ElemSection ms{sec};
   if (rhs) {  // (the reduction's blocks publish even when N = 0)
-    hipLaunchKernelGGL(k_assemble<true>, MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, xyz, slice_ptr, row_len, s_col,
-                       s_elem, active, m, G, val, diag, *rhs);
+    if (sec)
+      hipLaunchKernelGGL((k_assemble<true, ElemSection>), MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, xyz, slice_ptr,
+                         row_len, s_col, s_elem, active, ms, G, val, diag, *rhs);
+    else
+      hipLaunchKernelGGL((k_assemble<true, Material>), MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, xyz, slice_ptr, row_len,
+                         s_col, s_elem, active, m, G, val, diag, *rhs);
     return;
   }
   if (N <= 0) return;
-  hipLaunchKernelGGL(k_assemble<false>, MFEA_GRID(grid_rows(N)), N, xyz, slice_ptr, row_len, s_col, s_elem,
-                     active, m, G, val, diag, AsmRhs{});
+  if (sec)
+    hipLaunchKernelGGL((k_assemble<false, ElemSection>), MFEA_GRID(grid_rows(N)), N, xyz, slice_ptr, row_len, s_col,
+                       s_elem, active, ms, G, val, diag, AsmRhs{});
+  else
+    hipLaunchKernelGGL((k_assemble<false, Material>), MFEA_GRID(grid_rows(N)), N, xyz, slice_ptr, row_len, s_col,
+                       s_elem, active, m, G, val, diag, AsmRhs{});
 }
 
 void launch_assemble_colour(hipStream_t s, int colors, const int32_t* cstart, const int32_t* entry,
                             const int32_t* e2n, const int32_t* epos, const double* xyz, const uint8_t* active,
-                            Material m, int64_t G, int64_t N, double* val, double* diag) {
+                            Material m, int64_t G, int64_t N, double* val, double* diag, const double2* sec) {
   if (N > 0) (void)hipMemsetAsync(diag, 0, (size_t)6 * N * sizeof(double), s);
   for (int c = 0; c < colors; ++c) {
     const int64_t e0 = cstart[c], e1 = cstart[c + 1];
-    if (e1 > e0)
-      hipLaunchKernelGGL(k_assemble_colour, MFEA_GRID(grid_rows(e1 - e0)), e0, e1, entry, e2n, epos, xyz, active, m,
-                         G, N, val, diag);
+    if (e1 <= e0) continue;
+    if (sec)
+      hipLaunchKernelGGL(k_assemble_colour<ElemSection>, MFEA_GRID(grid_rows(e1 - e0)), e0, e1, entry, e2n, epos, xyz,
+                         active, ElemSection{sec}, G, N, val, diag);
+    else
+      hipLaunchKernelGGL(k_assemble_colour<Material>, MFEA_GRID(grid_rows(e1 - e0)), e0, e1, entry, e2n, epos, xyz,
+                         active, m, G, N, val, diag);
   }
 }
 
 void launch_assemble_elems(hipStream_t s, int64_t E, int64_t N, const int32_t* e2n, const int32_t* epos,
                            const double* xyz, const uint8_t* active, Material m, const int32_t* slice_ptr,
-                           const int32_t* row_len, int64_t G, double* val, double* diag) {
-  if (E > 0) hipLaunchKernelGGL(k_assemble_elems, MFEA_GRID(grid_rows(E)), E, e2n, epos, xyz, active, m, G, val);
+                           const int32_t* row_len, int64_t G, double* val, double* diag, const double2* sec) {
+  if (E > 0 && sec)
+    hipLaunchKernelGGL(k_assemble_elems<ElemSection>, MFEA_GRID(grid_rows(E)), E, e2n, epos, xyz, active,
+                       ElemSection{sec}, G, val);
+  else if (E > 0)
+    hipLaunchKernelGGL(k_assemble_elems<Material>, MFEA_GRID(grid_rows(E)), E, e2n, epos, xyz, active, m, G, val);
   if (N > 0) hipLaunchKernelGGL(k_diag_rows, MFEA_GRID(grid_rows(N)), N, slice_ptr, row_len, G, val, diag);
 }
 
@@ -944,9 +996,15 @@ void launch_reaction(hipStream_t s, int64_t row0, int64_t nrows, int64_t N,
 void launch_stress(hipStream_t s, int64_t E, const int32_t* e2n, const double* xyz,
                    const double* u, Material m, double max_strain, uint8_t* active,
                    double* stress, double* partials, unsigned* ticket, double* red_out,
-                   const uint8_t* owned, int32_t* fail_list, unsigned* fail_cnt) {
-  hipLaunchKernelGGL(k_stress, MFEA_GRID(grid_rows(E > 0 ? E : 1)), E, e2n, xyz, u, m, max_strain,
-                     active, stress, partials, ticket, red_out, owned, fail_list, fail_cnt);
+                   const uint8_t* owned, int32_t* fail_list, unsigned* fail_cnt, const double* Ee,
+                   const double* strength) {
+  if (Ee || strength)
+    hipLaunchKernelGGL(k_stress<ElemPost>, MFEA_GRID(grid_rows(E > 0 ? E : 1)), E, e2n, xyz, u,
+                       (ElemPost{m.E, Ee, strength}), max_strain, active, stress, partials, ticket, red_out, owned,
+                       fail_list, fail_cnt);
+  else
+    hipLaunchKernelGGL(k_stress<Material>, MFEA_GRID(grid_rows(E > 0 ? E : 1)), E, e2n, xyz, u, m, max_strain,
+                       active, stress, partials, ticket, red_out, owned, fail_list, fail_cnt);
 }
 
 void launch_unfail(hipStream_t s, const int32_t* fail_list, unsigned* cnt, uint8_t* active) {

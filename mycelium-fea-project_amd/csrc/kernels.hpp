@@ -79,6 +79,21 @@ struct Material {
   double E;     // for stress = E·ε (src/fea_solver.py:271)
 };
 
+// Per-element properties (mfea_set_element_props), indexed by element id.
+// ElemSection: one interleaved (EA_e, EI12_e) pair per element — a slot of the
+// assembly costs one 16-byte load.  ElemPost: E_e and max_strain_e of the post,
+// either NULL: the scalar.  The kernels are templates over Material / these
+// (no run-time choice inside them); a launcher picks the per-element
+// instantiation when its array argument is non-null.
+struct ElemSection {
+  const double2* sec;
+};
+struct ElemPost {
+  double E;
+  const double* Ee;
+  const double* strength;
+};
+
 // ---- launchers (defined in kernels.hip) -------------------------------------
 // The GAMG solves' RHS formed in the assembly's row pass (k_amg_rhs's work:
 // b = 0 − K_fk x_k of the free rows into r, the prescribed x of the others,
@@ -100,19 +115,21 @@ struct AsmRhs {
 void launch_assemble(hipStream_t s, int64_t N, const double* xyz, const int32_t* slice_ptr,
                      const int32_t* row_len, const int32_t* s_col, const int32_t* s_elem,
                      const uint8_t* active, Material m, int64_t G, double* val, double* diag,
-                     const AsmRhs* rhs = nullptr);
+                     const AsmRhs* rhs = nullptr, const double2* sec = nullptr);
 
 // element-centric assembly over an element colouring (symbolic.hpp
 // ElemColour; cstart on the host): diag zeroed, then one launch per colour
 void launch_assemble_colour(hipStream_t s, int colors, const int32_t* cstart, const int32_t* entry,
                             const int32_t* e2n, const int32_t* epos, const double* xyz, const uint8_t* active,
-                            Material m, int64_t G, int64_t N, double* val, double* diag);
+                            Material m, int64_t G, int64_t N, double* val, double* diag,
+                            const double2* sec = nullptr);
 
 // element pass (−S_e to both slots, one launch) + row pass (diagonal blocks
 // in slot order: K bit for bit the row gather's)
 void launch_assemble_elems(hipStream_t s, int64_t E, int64_t N, const int32_t* e2n, const int32_t* epos,
                            const double* xyz, const uint8_t* active, Material m, const int32_t* slice_ptr,
-                           const int32_t* row_len, int64_t G, double* val, double* diag);
+                           const int32_t* row_len, int64_t G, double* val, double* diag,
+                           const double2* sec = nullptr);
 
 void launch_rhs_init(hipStream_t s, int64_t N, int64_t nf, const int32_t* slice_ptr,
                      const int32_t* row_len, const int32_t* s_col, const double* val,
@@ -150,7 +167,8 @@ void launch_unfail(hipStream_t s, const int32_t* fail_list, unsigned* cnt, uint8
 void launch_stress(hipStream_t s, int64_t E, const int32_t* e2n, const double* xyz,
                    const double* u, Material m, double max_strain, uint8_t* active,
                    double* stress, double* partials, unsigned* ticket, double* red_out,
-                   const uint8_t* owned = nullptr, int32_t* fail_list = nullptr, unsigned* fail_cnt = nullptr);
+                   const uint8_t* owned = nullptr, int32_t* fail_list = nullptr, unsigned* fail_cnt = nullptr,
+                   const double* Ee = nullptr, const double* strength = nullptr);
 
 // ---- event-driven failure runs (events.hip) ---------------------------------
 // k_event_scan: the reaction of the top grip rows (launch_reaction's arguments;
@@ -177,6 +195,9 @@ struct EventScan {
   double *cnt_out, *smax_out;
   unsigned grid_r, grid_e;
   double *partials_r, *partials_e, *pmax;
+  // per-element strength (max_strain_e, or NULL): the scan then reduces
+  // min lam_e = max_strain_e / |ε_e| (identity +inf) into smax_out instead
+  const double* strength;
 };
 void launch_event_scan(hipStream_t s, EventScan q);
 int64_t event_scan_partials(int64_t n_top, int64_t n_elems);
@@ -201,6 +222,11 @@ struct EventApply {
   double* partials;
   unsigned* ticket;
   double *cnt_out, *lam_out;
+  // per-element forms: E_e of the stress row (or NULL: Emod); max_strain_e (or
+  // NULL) — then *smax holds the scan's min lam_e, lam is that value and
+  // element e fails when lam_e <= lam / (1 − tie_rtol)
+  const double* Ee;
+  const double* strength;
 };
 void launch_event_apply(hipStream_t s, const EventApply& q);
 // k_event_apply's failures undone: active again, event_of = -1, counter zero

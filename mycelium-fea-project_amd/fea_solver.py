@@ -172,9 +172,45 @@ def _grips(nodes, coords, tol):
     return top, bot
 
 
+PROP_COLUMNS = ("E", "A", "I", "max_strain")
+
+
+def read_element_props(path, n_elems):
+    """A per-element property file: CSV with a header, ``elem_id`` plus any
+    subset of E, A, I, max_strain; every element id 0 … n_elems − 1 exactly
+    once, in any order.  Returns {column: float64 array in element order}
+    (Engine.set_element_props's arguments); ValueError names what is wrong."""
+    df = pd.read_csv(path, float_precision="round_trip")  # (the values the file's digits stand for)
+    if "elem_id" not in df.columns:
+        raise ValueError(f"{path}: no elem_id column")
+    unknown = [c for c in df.columns if c != "elem_id" and c not in PROP_COLUMNS]
+    if unknown:
+        raise ValueError(f"{path}: unknown column(s) {unknown}; expected elem_id and any of {list(PROP_COLUMNS)}")
+    ids_f = df["elem_id"].values.astype(np.float64)
+    if not (np.isfinite(ids_f).all() and (ids_f == np.floor(ids_f)).all()):
+        raise ValueError(f"{path}: elem_id must hold integers")
+    ids = ids_f.astype(np.int64)
+    bad = ids[(ids < 0) | (ids >= n_elems)]
+    if bad.size:
+        raise ValueError(f"{path}: element id {int(bad[0])} outside 0..{n_elems - 1}")
+    count = np.bincount(ids, minlength=n_elems)
+    if (count > 1).any():
+        raise ValueError(f"{path}: duplicate element id {int(np.flatnonzero(count > 1)[0])}")
+    if (count == 0).any():
+        raise ValueError(f"{path}: missing element id {int(np.flatnonzero(count == 0)[0])} "
+                         f"({int((count == 0).sum())} of {n_elems} missing)")
+    out = {}
+    for c in PROP_COLUMNS:
+        if c in df.columns:
+            col = np.empty(n_elems, dtype=np.float64)
+            col[ids] = df[c].values.astype(np.float64)
+            out[c] = col
+    return out
+
+
 def fea_solver(results_dir, tol=GRIP_LENGTH, *, rtol=None, max_it=None, precond=None,
                out_format="python", verbose=True, nparts=1, npy=False, device_run=False,
-               events=False, tie_rtol=1e-9, max_events=None):
+               events=False, tie_rtol=1e-9, max_events=None, element_props=None):
     """The reference step loop (src/fea_solver.py:186-335) with the hot path on device.
 
     Reads <results_dir>/nodes.csv + elements.csv, runs N_STEPS load steps and
@@ -206,9 +242,17 @@ def fea_solver(results_dir, tol=GRIP_LENGTH, *, rtol=None, max_it=None, precond=
     the state at the failure load; force_displacement.csv holds (lam·span,
     lam·F₁) — and failure_events.csv lists event, lam, total_displacement,
     total_force, n_failed, n_active.  npy=True also writes event_of.npy (the
-    event that failed each element, -1 = none)."""
+    event that failed each element, -1 = none).
+
+    element_props (one process, one partition): a property file
+    (read_element_props) or a dict of per-element arrays E, A, I, max_strain —
+    a heterogeneous network (Engine.set_element_props); the columns not given
+    stay the module's constants.  Works with the ramp, device_run and events;
+    the record files and their formats do not change."""
     start_time = time.time()
     rank, world = dist_env()
+    if element_props is not None and (world > 1 or nparts > 1):
+        raise ValueError("element_props needs one process and one partition (world == 1, nparts == 1)")
     if events and (world > 1 or nparts > 1):
         raise ValueError("events needs one process and one partition (world == 1, nparts == 1)")
     if device_run and (world > 1 or nparts > 1):
@@ -240,6 +284,10 @@ def fea_solver(results_dir, tol=GRIP_LENGTH, *, rtol=None, max_it=None, precond=
     eng.set_mesh(coords, e2n)
     eng.set_bc(top, bot)
     eng.set_active(None)
+    if element_props is not None:
+        props = (element_props if isinstance(element_props, dict)
+                 else read_element_props(element_props, n_elems))
+        eng.set_element_props(**{k: np.ascontiguousarray(v, dtype=np.float64) for k, v in props.items()})
     opts = _opts(rtol, max_it, precond)
     node_owned, elem_owned = eng.ownership() if world > 1 else (None, None)
 
@@ -398,13 +446,24 @@ def main(argv=None):
     ap.add_argument("--parts", type=int, default=1,
                     help="partitions of the multi-GPU solve, all on this device (one process); "
                          "for one GPU per process launch with torch.distributed.run instead")
+    ap.add_argument("--element-props", metavar="FILE", default=None,
+                    help="per-element properties: CSV with a header, elem_id plus any of E,A,I,max_strain, "
+                         "every element exactly once (one process, one partition)")
     a = ap.parse_args(argv)
+    props = None
+    if a.element_props is not None:
+        try:
+            n_elems = len(pd.read_csv(os.path.join(a.results_dir, "elements.csv")))
+            props = read_element_props(a.element_props, n_elems)
+        except (ValueError, OSError) as e:
+            print(f"fea_solver: --element-props: {e}", file=sys.stderr)
+            sys.exit(2)
     N_STEPS, DISPLACEMENT_MAX, MAX_STRAIN, REG = a.n_steps, a.disp_max, a.max_strain, a.reg
     fea_solver(a.results_dir, tol=a.grip_length, rtol=a.rtol, max_it=a.max_it,
                precond={"gamg": _capi.PC_GAMG, "jacobi": _capi.PC_JACOBI,
                         "bjacobi": _capi.PC_BLOCK_JACOBI, "sor": _capi.PC_SOR, "icc": _capi.PC_ICC}[a.pc],
                out_format=a.format, nparts=a.parts, npy=a.npy, device_run=a.device_run,
-               events=a.events, tie_rtol=a.tie_rtol, max_events=a.max_events)
+               events=a.events, tie_rtol=a.tie_rtol, max_events=a.max_events, element_props=props)
 
 
 if __name__ == "__main__":

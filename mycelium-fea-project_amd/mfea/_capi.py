@@ -79,6 +79,11 @@ class EventOut(C.Structure):
                 ("n_active", C.c_int64)]
 
 
+class ElementProps(C.Structure):
+    """mfea_element_props (include/mfea.h): per-element columns, NULL = the scalar."""
+    _fields_ = [("E", C.c_void_p), ("A", C.c_void_p), ("I", C.c_void_p), ("max_strain", C.c_void_p)]
+
+
 class EventRecords(C.Structure):
     """mfea_event_records (include/mfea.h): where mfea_run_events writes each event's rows."""
     _fields_ = [("U", C.c_void_p), ("stress", C.c_void_p), ("active", C.c_void_p),
@@ -124,6 +129,8 @@ _sig = {
     "mfea_create": (C.c_int, [C.c_int, C.POINTER(_P)]),
     "mfea_destroy": (C.c_int, [_P]),
     "mfea_set_material": (C.c_int, [_P, C.c_double, C.c_double, C.c_double]),
+    "mfea_set_element_props": (C.c_int, [_P, C.POINTER(ElementProps)]),
+    "mfea_get_element_props": (C.c_int, [_P, _P, _P, _P, _P]),
     "mfea_set_mesh": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_uint32]),
     "mfea_set_bc": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P]),
     "mfea_set_active": (C.c_int, [_P, _P]),
@@ -453,6 +460,36 @@ class Engine:
         _check(_lib.mfea_set_mesh(self._h, xyz.shape[0], _ptr(xyz), e2n.shape[0], _ptr(e2n),
                                   MESH_SKIP_INVALID if skip_invalid else 0))
         self.n_nodes, self.n_elems = xyz.shape[0], e2n.shape[0]
+
+    def set_element_props(self, E=None, A=None, I=None, max_strain=None):
+        """Per-element modulus, section and failure strain (mfea_set_element_props):
+        each a contiguous float64 array of n_elems entries in the order of the
+        mesh's elements, or None for the scalar (set_material / the call's
+        max_strain).  All None: back to the uniform engine.  The library copies
+        the arrays."""
+        if not hasattr(self, "_xyz"):  # (no mesh yet: the library's MFEA_ESTATE)
+            _check(_lib.mfea_set_element_props(self._h, None))
+            return
+        cols, keep = ElementProps(), []
+        for name, v in (("E", E), ("A", A), ("I", I), ("max_strain", max_strain)):
+            if v is None:
+                continue
+            a = np.asarray(v)
+            if a.dtype != np.float64 or not a.flags.c_contiguous:
+                raise ValueError(f"{name} must be a contiguous float64 array")
+            if a.ndim != 1 or a.size != self.n_elems:
+                raise ValueError(f"{name} must have one entry per element ({self.n_elems})")
+            keep.append(a)
+            setattr(cols, name, _ptr(a))
+        _check(_lib.mfea_set_element_props(self._h, C.byref(cols)))
+
+    def element_props(self) -> dict:
+        """What the engine uses (mfea_get_element_props): E, A, I filled with the
+        handle's scalar where no array was set, max_strain NaN where none was."""
+        out = {k: np.empty(self.n_elems, dtype=np.float64) for k in ("E", "A", "I", "max_strain")}
+        _check(_lib.mfea_get_element_props(self._h, _ptr(out["E"]), _ptr(out["A"]), _ptr(out["I"]),
+                                           _ptr(out["max_strain"])))
+        return out
 
     def set_bc(self, top, bot):
         top = np.ascontiguousarray(top, dtype=np.int64).ravel()

@@ -82,6 +82,27 @@ def grips(xyz, tol=1.5):
     return top, bot
 
 
+# ---------------------------------------------------------------------------
+# Heterogeneous networks (Engine.set_element_props): sections from hyphal
+# diameters, strengths from a Weibull distribution.  Pure NumPy.
+# ---------------------------------------------------------------------------
+def section_from_diameter(d, t_wall):
+    """(A, I) of hollow hyphae of outer diameter d and wall thickness t_wall
+    (arrays or scalars, broadcast), with the reference's constants
+    (src/fea_solver.py:14-20): A = 3.14·((d/2)² − (d/2 − t)²), I = A·0.001."""
+    d = np.asarray(d, dtype=np.float64)
+    t = np.asarray(t_wall, dtype=np.float64)
+    A = 3.14 * ((d / 2) ** 2 - (d / 2 - t) ** 2)
+    return A, A * 0.001
+
+
+def weibull_strength(n, shape, scale, seed, floor=0.0):
+    """n failure strains scale·W, W ~ Weibull(shape) from
+    np.random.default_rng(seed), clipped below at floor."""
+    rng = np.random.default_rng(seed)
+    return np.clip(scale * rng.weibull(shape, n), floor, None)
+
+
 # benchmark configurations of BASELINE.json (tiles nx × ny)
 CONFIGS = {
     "C1_test_I": None,
