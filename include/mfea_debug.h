@@ -155,6 +155,21 @@ int mfea_debug_floating(mfea_handle* h, uint8_t* out);
  *   "amg_big_chunk" n    MFEA_PC_GAMG, one partition, chunk 0 in the solve's options: groups per
  *                        chunk of a planned batch that is not one graph of its own length
  *                        (8; 2..63).  Keeps K and the hierarchy's values when set.
+ *   "amg_l0_window" n    MFEA_PC_GAMG, one partition: rows per length-sorting window of level 0's
+ *                        SELL layouts (A_0's rows, P̃_0's and R̂_0's own labellings), a multiple of
+ *                        64; 0 (default): 1408 where "amg_fuse_l0" is wanted for the plan, else
+ *                        4096, the coarse levels' window.  At 1408 or 1024 rows the w = A u
+ *                        kernel and the closing check map rows by tiles of that many rows.
+ *                        Rebuilds the plan.  Read-only "amg_l0_window_used": the plan's window
+ *   "amg_fuse_l0" -1|0|1 MFEA_PC_GAMG, one partition, the compact unmerged cycle on a hierarchy of
+ *                        two levels or more whose level-0 window is 1408 or 1024 rows: level 0's
+ *                        up sweep and w = A u as one launch over block-local rows, k_amg_up_w
+ *                        (1), or as two (0); the same bits at the same window.  -1 (default): on
+ *                        (DESIGN.md §4.12).  Merged plans, SOR / ICC, the four-step cycle, the
+ *                        partitioned solves, and a plan whose largest block halo exceeds the
+ *                        launch's LDS keep the two launches.  Rebuilds the plan.  Read-only:
+ *                        "amg_fused_l0" (the fused launch is in use), "amg_fuse_max_halo",
+ *                        "amg_fuse_halo_cap" (rows)
  * Read-only: "sweep_colors", "sweep_pieces" (the last SOR / ICC plan), "asm_colours"
  * (the element colouring's colours once asm_kernel 1 or 2 has run; 0 before),
  * "element_props" (1 while mfea_set_element_props holds any per-element column, else 0).

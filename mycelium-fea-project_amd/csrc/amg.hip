@@ -1448,13 +1448,28 @@ __global__ __launch_bounds__(kBlock) void k_amg_start(SellOp op, const uint8_t* 
   if (threadIdx.x == 0) cg_state_init(st, red_out[0], red_out[1], rtol, atol, norm, max_it, reg);
 }
 
-template <int ND, bool FIRST, int BS, bool DIST, int KW = 1>
+// The tile mapping of rows (AmgCg::w_tile = 2·BS; one partition, rows [0, n)):
+// f(i) for rows t and t + BS of every tile of the block, waves wholly past the
+// end skipped.  The w kernel, the closing check and k_amg_up_w share it.
+template <int BS, class F>
+__device__ __forceinline__ void tile_rows(int64_t n, F&& f) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nt = (n + 2 * BS - 1) / (2 * BS);
+  for (int64_t tile = xcd_block(); tile < nt; tile += gridDim.x)
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      const int64_t i = tile * (2 * BS) + m * BS + threadIdx.x;
+      if (i - lane < n) f(i);
+    }
+}
+
+template <int ND, bool FIRST, int BS, bool DIST, int KW = 1, bool TILE = false>
 __global__ __launch_bounds__(BS) void k_amg_cg_w(int j, AmgLevD L0, AmgCg cg, Slot* slots, double* part,
                                                  AmgDist d) {
   double acc[4] = {0.0, 0.0, 0.0, 0.0};
   const int64_t stride = (int64_t)gridDim.x * BS;
   const int lane = threadIdx.x & 63;
-  for (int64_t i = cg.lo64() + xcd_block() * BS + threadIdx.x; i - lane < cg.hi; i += stride) {
+  auto row = [&](int64_t i) {
     const int64_t ii = i < cg.hi ? i : cg.hi - 1;
     int64_t base;
     int w;
@@ -1465,7 +1480,7 @@ __global__ __launch_bounds__(BS) void k_amg_cg_w(int j, AmgLevD L0, AmgCg cg, Sl
 #pragma unroll
     for (int a = 0; a < ND; ++a) y[a] = 0.0;
     sell_mac<ND, false, KW, true>(L0.A.col, L0.A.sym, L0.A.npos, base, w, cg.u, y);
-    if (i < cg.lo || i >= cg.hi) continue;
+    if (i < cg.lo || i >= cg.hi) return;
     if constexpr (DIST) {  // couplings to free rows of other partitions: K_ig u_g
       for (int t = d.gptr[i]; t < d.gptr[i + 1]; ++t) {
         const int64_t q = d.gslot[t];
@@ -1488,9 +1503,108 @@ __global__ __launch_bounds__(BS) void k_amg_cg_w(int j, AmgLevD L0, AmgCg cg, Sl
       acc[2] = fma(r[a], r[a], acc[2]);
       acc[3] = fma(u[a], u[a], acc[3]);
     }
+  };
+  if constexpr (TILE) {
+    tile_rows<BS>(cg.hi, row);
+  } else {
+    for (int64_t i = cg.lo64() + xcd_block() * BS + threadIdx.x; i - lane < cg.hi; i += stride) row(i);
   }
   store_block_partial<BS>(acc, part_buf(part, FIRST ? 0 : ((j & 1) ^ 1)));
   if (FIRST && blockIdx.x == 0 && threadIdx.x == 0) {
+    Slot s0;
+    s0.v[0] = s0.v[1] = s0.v[2] = s0.v[3] = 0.0;
+    s0.alpha = s0.beta = s0.res = 0.0;
+    s0.flag = kInit;
+    s0.pad = 0;
+    slots[0] = s0;
+  }
+}
+
+// Level 0's up sweep and w = A_0 u as phases of ONE launch over the tiles of
+// AmgCg::w_tile = 2·BS rows (amg.hpp AmgFusePlan).  The w launch gathers the
+// up launch's output from neighbouring rows, which is why they were two; in
+// the depth-first order a tile's rows reference few rows outside it (C3,
+// 1408-row tiles: 2–3 %), so a workgroup that forms its tile's u can form
+// that halo too and gather from LDS.
+//   Phase 1: u = c_0 + P̃_0 e_1 for the tile's rows — k_amg_up's row body (one
+//   lane per row): the same loads, the same fma chain, the store to cg.u — and
+//   into LDS; then the tile's halo rows, the same body on their own P̃_0 rows
+//   (each lane its own slice), into LDS only.
+//   Phase 2: behind the barrier, k_amg_cg_w's row body with u from LDS
+//   through the local columns: sell_mac's sums in slot order on the same
+//   values (cg.u holds f32, LDS the same f32), r, the store of w and the four
+//   sums as there; the partials per block as k_amg_cg_w<…, TILE> publishes them.
+template <int ND, int BS, int KW>
+__global__ __launch_bounds__(BS) void k_amg_up_w(int j, int first, AmgLevD L, AmgLevD N, AmgCg cg, AmgFuseD f,
+                                                 Slot* slots, double* part) {
+  extern __shared__ float ul[];  // [2·BS + hcap][ND]: the tile's u, then its halo's
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  const AmgMatD& T = L.PT;
+  const int lane = threadIdx.x & 63;
+  const int64_t n = cg.hi;
+  const int64_t nt = (n + 2 * BS - 1) / (2 * BS);
+  const float* src = N.coarsest ? N.x : N.e;
+  for (int64_t tile = xcd_block(); tile < nt; tile += gridDim.x) {
+    const int64_t r0 = tile * (2 * BS);
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      const int64_t a = r0 + m * BS + threadIdx.x;
+      if (a - lane >= n) continue;
+      const int64_t aa = a < n ? a : n - 1;
+      int64_t base;
+      int w;
+      slice_of(T, aa, base, w);
+      const int64_t i = L.pt_row[aa];
+      float y[ND];
+      vload<ND>(L.t, i, y);
+      sell_mac<ND, false, 3>(T.col, T.val32, T.npos, base, w, src, y);
+      if (a < n) {
+        vstore<ND>(cg.u, i, y);
+        vstore<ND>(ul, i - r0, y);
+      }
+    }
+    const int h0 = f.hptr[tile], h1 = f.hptr[tile + 1];
+    for (int h = h0 + (int)threadIdx.x; h < h1; h += BS) {
+      const int64_t a = f.hpt[h], i = f.hrow[h];
+      const int sa = T.sptr[a >> 6], sb = T.sptr[(a >> 6) + 1];
+      const int64_t base = (int64_t)sa * 64 + (a & 63);
+      float y[ND];
+      vload<ND>(L.t, i, y);
+      sell_mac<ND, false, 3>(T.col, T.val32, T.npos, base, sb - sa, src, y);
+      vstore<ND>(ul, 2 * BS + (h - h0), y);
+    }
+    __syncthreads();
+    // (the thread's two rows one after the other: run in lockstep, both rows'
+    // loads ahead of either's FMAs, the short rows of the window's second
+    // half take the long first half's steps — measured slower, §4.12)
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      const int64_t i = r0 + m * BS + threadIdx.x;
+      if (i - lane >= n) continue;
+      const int64_t ii = i < n ? i : n - 1;
+      int64_t base;
+      int w;
+      slice_of(L.A, ii, base, w);
+      double y[ND], u[ND], r[ND];
+      vload<ND>(ul, ii - r0, u);
+      vload<ND>(cg.r, ii, r);
+#pragma unroll
+      for (int a = 0; a < ND; ++a) y[a] = 0.0;
+      sell_mac<ND, false, KW, true>(f.lcol, L.A.sym, L.A.npos, base, w, (const float*)ul, y);
+      if (i >= n) continue;
+      vstore<ND>(cg.w, i, y);
+#pragma unroll
+      for (int a = 0; a < ND; ++a) {
+        acc[0] = fma(r[a], u[a], acc[0]);
+        acc[1] = fma(y[a], u[a], acc[1]);
+        acc[2] = fma(r[a], r[a], acc[2]);
+        acc[3] = fma(u[a], u[a], acc[3]);
+      }
+    }
+    if (tile + gridDim.x < nt) __syncthreads();  // the next tile overwrites ul
+  }
+  store_block_partial<BS>(acc, part_buf(part, first ? 0 : ((j & 1) ^ 1)));
+  if (first && blockIdx.x == 0 && threadIdx.x == 0) {
     Slot s0;
     s0.v[0] = s0.v[1] = s0.v[2] = s0.v[3] = 0.0;
     s0.alpha = s0.beta = s0.res = 0.0;
@@ -1573,20 +1687,25 @@ __global__ __launch_bounds__(kCgBS) void k_amg_px_replay(AmgCg cg, const Slot* s
 // REPLAY (option amg_lazy_px): each row also runs the chunk's p, x chain
 // (px_row) — own-row work on other arrays, behind the row's load of r; the
 // ‖r‖² chain and its partials are untouched.
-template <int ND, int BS, bool REPLAY = false>
+template <int ND, int BS, bool REPLAY = false, bool TILE = false>
 __global__ __launch_bounds__(BS) void k_amg_rnorm(AmgCg cg, double* cpart, const Slot* slots, AmgPx px) {
   __shared__ PxLive live;
   if constexpr (REPLAY) px_records(slots, px, live);
   double acc[4] = {0.0, 0.0, 0.0, 0.0};
   const int64_t stride = (int64_t)gridDim.x * BS;
   const int lane = threadIdx.x & 63;
-  for (int64_t i = cg.lo64() + xcd_block() * BS + threadIdx.x; i - lane < cg.hi; i += stride) {
-    if (i < cg.lo || i >= cg.hi) continue;
+  auto row = [&](int64_t i) {
+    if (i < cg.lo || i >= cg.hi) return;
     double r[ND];
     vload<ND>(cg.r, i, r);
     if constexpr (REPLAY) px_row<ND>(cg, px, live, i);
 #pragma unroll
     for (int a = 0; a < ND; ++a) acc[2] = fma(r[a], r[a], acc[2]);
+  };
+  if constexpr (TILE) {
+    tile_rows<BS>(cg.hi, row);
+  } else {
+    for (int64_t i = cg.lo64() + xcd_block() * BS + threadIdx.x; i - lane < cg.hi; i += stride) row(i);
   }
   store_block_partial<BS>(acc, cpart);
 }
@@ -1745,7 +1864,12 @@ static dim3 rows_grid(int64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBl
 // 768 whose grid fits kCgMaxG blocks in one pass — at C3 704 × 478 blocks
 // instead of 768 × 438: two blocks on every CU carry 1,408 rows instead of
 // 1,536 where 74 CUs got one (the SpMV is one pass of latency-bound rows).
+// cg.w_tile > 0 (the level-0 blocks of the halo plan, AmgCg): w_tile / 2
+// threads, one block per tile up to kCgMaxG blocks (C5: 2,367 tiles of 1408
+// rows, 4–5 per block).
+static bool w_tiled(const AmgCg& cg) { return cg.w_tile > 0 && cg.lo == 0; }
 int amg_w_block(const AmgCg& cg) {
+  if (w_tiled(cg)) return cg.w_tile / 2;
   if (cg.w_block > 0) return cg.w_block;
   const int64_t n = cg.hi > cg.lo ? cg.hi - cg.lo64() : 0;
   if (n <= (int64_t)kCgMaxG * kCgBS) return kCgBS;
@@ -1756,7 +1880,7 @@ int amg_w_block(const AmgCg& cg) {
 }
 int64_t amg_w_grid(const AmgCg& cg) {
   const int64_t n = cg.hi > cg.lo ? cg.hi - cg.lo64() : 0;
-  const int bs = amg_w_block(cg);
+  const int bs = w_tiled(cg) ? cg.w_tile : amg_w_block(cg);  // rows per block and pass
   const int64_t g = (n + bs - 1) / bs;
   return g < 1 ? 1 : (g > kCgMaxG ? kCgMaxG : g);
 }
@@ -2064,12 +2188,16 @@ static void compact_nd(hipStream_t s, const AmgLevD* lev, int nlev, const AmgCg&
     const int kc = cg.coll;
     for (int l = l0; l < kc; ++l) down_nd<ND>(s, lev[l], lev[l + 1], gate);
     vapply_nd<ND>(s, lev[kc], gate);
-    for (int l = kc - 1; l >= l0; --l) up_te<ND, float>(s, lev[l], lev[l + 1], l == 0 ? cg.u : lev[l].e, gate);
+    for (int l = kc - 1; l >= l0; --l) {
+      if (l == 0 && cg.skip_up0) break;  // (k_amg_up_w forms u)
+      up_te<ND, float>(s, lev[l], lev[l + 1], l == 0 ? cg.u : lev[l].e, gate);
+    }
     return;
   }
   const int top = nlev - 1;  // the coarsest level's output is its x
   for (int l = l0; l < top; ++l) down_nd<ND>(s, lev[l], lev[l + 1], gate);
   for (int l = top - 1; l >= l0; --l) {
+    if (l == 0 && cg.skip_up0) break;
     if (l == 0) up_te<ND, float>(s, lev[0], lev[1], cg.u, gate);
     else up_te<ND, float>(s, lev[l], lev[l + 1], lev[l].e, gate);
   }
@@ -2211,9 +2339,28 @@ static void w_bs(hipStream_t s, int j, bool first, const AmgLevD& L0, const AmgC
     else hipLaunchKernelGGL((k_amg_cg_w<ND, false, BS, false>), g, dim3(BS), 0, s, j, L0, cg, slots, part, dd);
   }
 }
+// the tile mapping (AmgCg::w_tile; one partition)
+template <int ND, int BS>
+static void w_tile_bs(hipStream_t s, int j, bool first, const AmgLevD& L0, const AmgCg& cg, Slot* slots,
+                      double* part) {
+  const dim3 g((unsigned)amg_w_grid(cg));
+  const AmgDist dd{};
+  if (cg.w_k == 2) {
+    if (first) hipLaunchKernelGGL((k_amg_cg_w<ND, true, BS, false, 2, true>), g, dim3(BS), 0, s, j, L0, cg, slots, part, dd);
+    else hipLaunchKernelGGL((k_amg_cg_w<ND, false, BS, false, 2, true>), g, dim3(BS), 0, s, j, L0, cg, slots, part, dd);
+  } else {
+    if (first) hipLaunchKernelGGL((k_amg_cg_w<ND, true, BS, false, 1, true>), g, dim3(BS), 0, s, j, L0, cg, slots, part, dd);
+    else hipLaunchKernelGGL((k_amg_cg_w<ND, false, BS, false, 1, true>), g, dim3(BS), 0, s, j, L0, cg, slots, part, dd);
+  }
+}
 template <int ND>
 static void w_nd(hipStream_t s, int j, bool first, const AmgLevD& L0, const AmgCg& cg, Slot* slots,
                  double* part, const AmgDist* d) {
+  if (w_tiled(cg) && !d) {
+    if (cg.w_tile == 1408) w_tile_bs<ND, 704>(s, j, first, L0, cg, slots, part);
+    else w_tile_bs<ND, 512>(s, j, first, L0, cg, slots, part);
+    return;
+  }
   switch (amg_w_block(cg)) {
     case 512: w_bs<ND, 512>(s, j, first, L0, cg, slots, part, d); break;
     case 576: w_bs<ND, 576>(s, j, first, L0, cg, slots, part, d); break;
@@ -2230,10 +2377,35 @@ void launch_amg_cg_w(hipStream_t s, int nd, int j, bool first, const AmgLevD& L0
   else w_nd<3>(s, j, first, L0, cg, slots, part, d);
 }
 
+template <int ND, int BS>
+static void up_w_bs(hipStream_t s, int j, bool first, const AmgLevD& L0, const AmgLevD& L1, const AmgCg& cg,
+                    const AmgFuseD& f, Slot* slots, double* part) {
+  const dim3 g((unsigned)amg_w_grid(cg));
+  const size_t lds = (size_t)(2 * BS + f.hcap) * ND * sizeof(float);
+  const int fi = first ? 1 : 0;
+  if (cg.w_k == 2) hipLaunchKernelGGL((k_amg_up_w<ND, BS, 2>), g, dim3(BS), lds, s, j, fi, L0, L1, cg, f, slots, part);
+  else hipLaunchKernelGGL((k_amg_up_w<ND, BS, 1>), g, dim3(BS), lds, s, j, fi, L0, L1, cg, f, slots, part);
+}
+void launch_amg_up_w(hipStream_t s, int nd, int j, bool first, const AmgLevD& L0, const AmgLevD& L1,
+                     const AmgCg& cg, const AmgFuseD& f, Slot* slots, double* part) {
+  if (cg.w_tile == 1408) {
+    if (nd == 2) up_w_bs<2, 704>(s, j, first, L0, L1, cg, f, slots, part);
+    else up_w_bs<3, 704>(s, j, first, L0, L1, cg, f, slots, part);
+  } else {
+    if (nd == 2) up_w_bs<2, 512>(s, j, first, L0, L1, cg, f, slots, part);
+    else up_w_bs<3, 512>(s, j, first, L0, L1, cg, f, slots, part);
+  }
+}
+
 // the w kernel's launch geometry (w_nd / w_bs), so the partials match its own
 template <int ND, bool REPLAY>
 static void rnorm_nd(hipStream_t s, const AmgCg& cg, double* cpart, const Slot* slots, const AmgPx& px) {
   const dim3 g((unsigned)amg_w_grid(cg));
+  if (w_tiled(cg)) {
+    if (cg.w_tile == 1408) hipLaunchKernelGGL((k_amg_rnorm<ND, 704, REPLAY, true>), g, dim3(704), 0, s, cg, cpart, slots, px);
+    else hipLaunchKernelGGL((k_amg_rnorm<ND, 512, REPLAY, true>), g, dim3(512), 0, s, cg, cpart, slots, px);
+    return;
+  }
   switch (amg_w_block(cg)) {
     case 512: hipLaunchKernelGGL((k_amg_rnorm<ND, 512, REPLAY>), g, dim3(512), 0, s, cg, cpart, slots, px); break;
     case 576: hipLaunchKernelGGL((k_amg_rnorm<ND, 576, REPLAY>), g, dim3(576), 0, s, cg, cpart, slots, px); break;

@@ -55,6 +55,7 @@ inline void row_stable_sort(It b, It e, Less less) {
 
 
 constexpr int kAmgMaxLevels = 32;
+constexpr int64_t kAmgSortWindow = 4096;  // rows per SELL-C-σ sorting window (64 slices)
 
 // A node-block matrix pattern in SELL-64 layout: slice s covers rows
 // [64 s, 64 s + 64), its entries occupy slot rows sptr[s] .. sptr[s+1]-1;
@@ -129,6 +130,7 @@ struct AmgPlan {
   int world = 1;
   int n_dist = 0;
   bool spatial = false;  // rows labelled in Z-order (AmgLayout)
+  int64_t l0_window = kAmgSortWindow;  // level 0's sorting window (AmgLayout)
 };
 
 // The distributed hierarchy (multi-GPU GAMG): ONE global
@@ -178,6 +180,13 @@ struct AmgLayout {
   // cycle's sweeps read A and R̂, which has labels of its own); false: by
   // A + R length (the four-step cycle's resid and restriction)
   bool by_a = false;
+  // rows per length-sorting window of level 0 (a multiple of 64): A_0's rows
+  // and P̃_0's and R̂_0's own labellings.  Coarse levels keep kAmgSortWindow.
+  // Inside a window the labels are a permutation, so a block of l0_window
+  // consecutive level-0 rows holds the same rows under all three labellings
+  // and, in the depth-first order, nearly all of its rows' neighbours
+  // (AmgFusePlan).  Unsplit plans only.
+  int64_t l0_window = 4096;
 };
 
 // Builds the hierarchy for the free rows [0, P.n_free) of P with the element
@@ -298,6 +307,32 @@ struct AmgMerge {
 // on = false (nothing built) unless the plan's cycle collapses at level 2
 // (coll.kc == 2) on one partition.
 std::string build_amg_merge(const AmgPlan& plan, const AmgCollapse& coll, AmgMerge& out);
+
+// The block halo plan of level 0 (amg.hip k_amg_up_w: the last prolongation
+// u = c_0 + P̃_0 e_1 and the CG's w = A_0 u as phases of one launch).  Level
+// 0's rows in blocks of B = plan.l0_window consecutive rows, block b owning
+// rows [bB, (b+1)B): a workgroup forms its own rows' u into LDS, and the few
+// rows of other blocks its A_0 entries reference — the block's HALO — once
+// more from c_0, P̃_0 and e_1, so every gather of phase 2 is a local one.
+// on = false (and `why`) unless the plan is an unsplit one of two levels or
+// more whose P̃_0 labelling keeps every block's rows inside the block, and
+// whose largest halo is at most halo_cap rows (the kernel's LDS; never
+// exceeded: a plan that does not fit keeps its two launches).
+struct AmgFusePlan {
+  bool on = false;
+  std::string why;               // why not, when off
+  int64_t B = 0;                 // rows per block
+  int64_t n_blocks = 0;
+  int64_t max_halo = 0;          // largest block halo, rows
+  int64_t cut = 0, offdiag = 0;  // A_0 couplings leaving their block / all off-diagonal ones
+  std::vector<int32_t> hptr;     // n_blocks + 1: block b's halo is [hptr[b], hptr[b+1])
+  std::vector<int32_t> hrow;     // the halo rows: level-0 rows, ascending per block
+  std::vector<int32_t> hpt;      // … and their P̃_0 rows (pt_row's inverse)
+  // parallel to A_0's col: the own row − bB, or B + the index in the block's
+  // halo; 0xFFFF on padding (read as −1 by the kernel: B + halo ≤ 32767)
+  std::vector<uint16_t> lcol;
+};
+std::string build_amg_fuse(const AmgPlan& plan, int64_t halo_cap, AmgFusePlan& out);
 
 // Block-Jacobi multicolour sweeps over A_0 (MFEA_PC_SOR, MFEA_PC_ICC; sweep.hip):
 // level-0 rows in blocks of `rows_per_block` consecutive rows (one workgroup

@@ -233,8 +233,10 @@ __device__ __forceinline__ void slice_of(const AmgMatD& M, int64_t row, int64_t&
 template <int ND>
 constexpr int mac_unroll() { return ND == 2 ? 4 : 2; }
 
-template <int ND, int U, int S, bool SUB, bool SYM, class TV, class XP, class C>
-__device__ __forceinline__ void sell_step(const int32_t* __restrict__ col, const TV* __restrict__ val,
+// (CI: the column type — int32_t rows, or a block's int16_t local columns,
+// k_amg_up_w; −1 marks padding in both)
+template <int ND, int U, int S, bool SUB, bool SYM, class TV, class XP, class C, class CI>
+__device__ __forceinline__ void sell_step(const CI* __restrict__ col, const TV* __restrict__ val,
                                           int64_t base, int k, int ws, int sub, XP x, C* y) {
   int32_t c[U];
   int64_t q[U];
@@ -271,8 +273,8 @@ __device__ __forceinline__ void sell_step(const int32_t* __restrict__ col, const
   }
 }
 // one step of the smallest of 1, 2, 4, … UMAX slots covering rem (> 0)
-template <int ND, int UMAX, int S, bool SUB, bool SYM, class TV, class XP, class C>
-__device__ __forceinline__ int sell_step_by(const int32_t* __restrict__ col, const TV* __restrict__ val,
+template <int ND, int UMAX, int S, bool SUB, bool SYM, class TV, class XP, class C, class CI>
+__device__ __forceinline__ int sell_step_by(const CI* __restrict__ col, const TV* __restrict__ val,
                                             int64_t base, int k, int rem, int ws, int sub, XP x, C* y) {
   if (UMAX >= 16 && rem > 8) {
     sell_step<ND, (UMAX >= 16 ? 16 : 1), S, SUB, SYM>(col, val, base, k, ws, sub, x, y);
@@ -300,8 +302,8 @@ __device__ __forceinline__ int sell_step_by(const int32_t* __restrict__ col, con
 // fixed U = 8 issued 8 loads per lane for the ≈ 1–2 slots each of the 8
 // lanes of a C3 R̂ row holds: the down sweep's vector-memory instructions
 // were three quarters padding.)  The branches are wave-uniform.
-template <int ND, int UMAX, int S, bool SUB, bool SYM, class TV, class XP, class C>
-__device__ __forceinline__ void sell_steps(const int32_t* __restrict__ col, const TV* __restrict__ val,
+template <int ND, int UMAX, int S, bool SUB, bool SYM, class TV, class XP, class C, class CI>
+__device__ __forceinline__ void sell_steps(const CI* __restrict__ col, const TV* __restrict__ val,
                                            int64_t base, int wu, int ws, int sub, XP x, C* y) {
   for (int k = 0; k < wu;) k += sell_step_by<ND, UMAX, S, SUB, SYM>(col, val, base, k, wu - k, ws, sub, x, y);
 }
@@ -310,8 +312,8 @@ __device__ __forceinline__ void sell_steps(const int32_t* __restrict__ col, cons
 // level-0 slices are ≤ 4 wide for 98 % of the waves, stays at K = 1 (a 2U path
 // put it at 139 VGPRs, one 768-thread block per CU); the streaming level-0
 // kernels use K = 2; the restrictions and the latency-bound coarse levels K = 3.
-template <int ND, bool SUB, int K = 2, bool SYM = false, class TV, class XP, class C>
-__device__ __forceinline__ void sell_mac(const int32_t* __restrict__ col, const TV* __restrict__ val,
+template <int ND, bool SUB, int K = 2, bool SYM = false, class TV, class XP, class C, class CI>
+__device__ __forceinline__ void sell_mac(const CI* __restrict__ col, const TV* __restrict__ val,
                                          int64_t /*npos*/, int64_t base, int w,
                                          XP x, C* y) {
   constexpr int UMAX = mac_unroll<ND>() << (K - 1);

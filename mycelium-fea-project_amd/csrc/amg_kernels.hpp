@@ -152,6 +152,13 @@ struct AmgCg {
   __host__ __device__ int64_t lo64() const { return lo & ~(int64_t)63; }
   int w_block = 0;  // w = A u kernel threads per block (0: by size)
   int w_k = 1;      // w = A u: 2 — slices up to 2U blocks wide in one round trip (sell_mac's K)
+  // > 0 (one partition, lo = 0): the w kernel, the closing check and the fused
+  // k_amg_up_w map rows by TILES of w_tile consecutive rows — block b (XCD-aware
+  // numbering) takes tiles b, b + grid, …, thread t of its w_tile / 2 threads
+  // rows t and t + w_tile / 2 of the tile — the level-0 blocks of AmgFuseD, so
+  // the three kernels publish the same partials.  0: the grid-stride mapping.
+  int w_tile = 0;
+  int skip_up0 = 0;  // the compact cycle leaves level 0's up sweep to k_amg_up_w
   const int32_t* row0 = nullptr;  // level-0 row → Pattern (row-order) free row
   double* x = nullptr;
   double* p = nullptr;
@@ -307,6 +314,26 @@ void launch_amg_cg_init(hipStream_t s, int nd, const AmgLevD& L0, const AmgCg& c
 // parity; first: slots[0] = INIT, parity 0
 void launch_amg_cg_w(hipStream_t s, int nd, int j, bool first, const AmgLevD& L0, const AmgCg& cg,
                      Slot* slots, double* part, const AmgDist* d = nullptr);
+// The block halo plan on the device (amg.hpp AmgFusePlan; uploaded once per
+// hierarchy).  The blocks are the tiles of AmgCg::w_tile rows.
+struct AmgFuseD {
+  int on = 0;
+  int hcap = 0;                     // halo rows the launch's LDS holds (≥ the largest halo)
+  const int32_t* hptr = nullptr;    // per tile: its halo [hptr[b], hptr[b+1])
+  const int32_t* hrow = nullptr;    // halo row: level-0 row
+  const int32_t* hpt = nullptr;     // halo row: its P̃_0 row
+  const int16_t* lcol = nullptr;    // A_0 position: local column (−1: padding)
+};
+// The tile sizes k_amg_up_w is built for (704- and 512-thread blocks, two rows
+// per thread) and the LDS a launch may take for u: own rows + halo
+constexpr int64_t kAmgFuseLds = 48 * 1024;
+inline bool amg_fuse_tile_ok(int64_t B) { return B == 1408 || B == 1024; }
+inline int64_t amg_fuse_halo_cap(int nd, int64_t B) { return kAmgFuseLds / (4 * nd) - B; }
+// the last up sweep u = c_0 + P̃_0 e_1 (into cg.u and LDS, halo rows into LDS
+// only) and w = A_0 u with the partials of launch_amg_cg_w, one launch; the
+// V-cycle before it ran with cg.skip_up0
+void launch_amg_up_w(hipStream_t s, int nd, int j, bool first, const AmgLevD& L0, const AmgLevD& L1,
+                     const AmgCg& cg, const AmgFuseD& f, Slot* slots, double* part);
 // inv[n_rows]: Pattern row → level-0 row of cg.row0, −1 elsewhere
 void launch_amg_row0_inverse(hipStream_t s, const AmgCg& cg, int32_t* inv, int64_t n_rows);
 // launch_cg_rhs (precond 2) + launch_cg_init_finalize + launch_amg_cg_init as

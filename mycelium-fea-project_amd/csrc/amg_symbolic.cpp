@@ -6,7 +6,7 @@
 //      index lists reference CSR entries: aggregation, P, R = Pᵀ, A·P and
 //      A_{l+1} = Pᵀ A P (Gustavson, fixed order);
 //   2. the device layout: every level's rows are relabelled so that, inside
-//      windows of kSortWindow consecutive rows, longer rows come first
+//      windows of kAmgSortWindow consecutive rows, longer rows come first
 //      (SELL-C-σ, C = 64): the 64 rows of a slice then have nearly equal
 //      lengths and a slice's width (its longest row) stops padding the
 //      others.  Natural (DFS / aggregate) order is kept across windows, so
@@ -26,8 +26,6 @@
 namespace mfea {
 
 namespace {
-
-constexpr int64_t kSortWindow = 4096;  // rows per SELL-C-σ sorting window (64 slices)
 
 struct Csr {
   int64_t n = 0;
@@ -302,13 +300,13 @@ std::string coarsen(LevelCsr& L, Csr& An) {
 }
 
 // ---- stage 2: relabelled SELL layouts -----------------------------------------
-// new = perm[old]: inside windows of kSortWindow rows, rows by descending key
+// new = perm[old]: inside windows of `window` rows, rows by descending key
 // (stable: ties keep natural order).  own: rows grouped by rank first
 // (owner-major, natural order inside a rank), the windows inside each rank's
 // segment; bounds (world + 1) receives the segments' first new rows.
 std::vector<int32_t> sort_perm(const std::vector<int64_t>& key, const std::vector<int32_t>* own = nullptr,
                                int world = 1, std::vector<int64_t>* bounds = nullptr,
-                               const std::vector<int32_t>* base = nullptr) {
+                               const std::vector<int32_t>* base = nullptr, int64_t window = kAmgSortWindow) {
   const int64_t n = (int64_t)key.size();
   std::vector<int32_t> order(n), perm(n);
   if (base) order = *base;  // a base order of the rows instead of the natural one (Z-order)
@@ -322,7 +320,7 @@ std::vector<int32_t> sort_perm(const std::vector<int64_t>& key, const std::vecto
   }
   std::vector<std::pair<int64_t, int64_t>> win;  // the sorting windows, independent
   for (size_t g = 0; g + 1 < seg.size(); ++g)
-    for (int64_t w0 = seg[g]; w0 < seg[g + 1]; w0 += kSortWindow) win.emplace_back(w0, std::min(seg[g + 1], w0 + kSortWindow));
+    for (int64_t w0 = seg[g]; w0 < seg[g + 1]; w0 += window) win.emplace_back(w0, std::min(seg[g + 1], w0 + window));
   par_for((int64_t)win.size() * kChunkRows / 16, [&](int64_t lo, int64_t hi, int) {
     const int64_t a = lo * 16 / kChunkRows, b = hi * 16 / kChunkRows;
     for (int64_t k = a; k < b && k < (int64_t)win.size(); ++k)
@@ -626,6 +624,10 @@ std::string build_amg(const Pattern& P, const std::vector<uint8_t>& active, int 
     spatial = off > 0 && (double)far > lay.far_frac * (double)off;
   }
   plan.spatial = spatial;
+  // level 0's window (AmgLayout): its A rows, and P̃_0's and R̂_0's labellings
+  if (lay.l0_window < 64 || lay.l0_window % 64) return "AMG level-0 sorting window: a positive multiple of 64";
+  const int64_t win0 = dist ? kAmgSortWindow : lay.l0_window;
+  plan.l0_window = win0;
   std::vector<double> cxyz;  // natural-order coordinates of the current level's rows
   std::vector<std::vector<int32_t>> bases(nlev);  // per level: its Z-order (spatial)
   if (spatial) {
@@ -658,7 +660,7 @@ std::string build_amg(const Pattern& P, const std::vector<uint8_t>& active, int 
       }
     }
     perm[l] = sort_perm(key, om ? &own[l] : nullptr, world, om ? &plan.lev[l].own : nullptr,
-                        spatial ? &base : nullptr);
+                        spatial ? &base : nullptr, l == 0 ? win0 : kAmgSortWindow);
     bases[l] = std::move(base);
     if (om) {
       plan.lev[l].owner.assign(n, 0);
@@ -699,7 +701,7 @@ std::string build_amg(const Pattern& P, const std::vector<uint8_t>& active, int 
       for (int64_t i = 0; i < L.A.n; ++i) key[i] = L.AP.len(i);
       const bool om = dist && l < n_dist;
       pap = sort_perm(key, om ? &own[l] : nullptr, world, om ? &out.ap_own : nullptr,
-                      spatial ? &bases[l] : nullptr);
+                      spatial ? &bases[l] : nullptr, l == 0 ? win0 : kAmgSortWindow);
       if (!(err = layout(L.AP, pap, &perm[l + 1], out.AP, eAP)).empty()) return err;
       if (om) {
         out.aprow.assign(L.A.n, 0);
@@ -752,7 +754,7 @@ std::string build_amg(const Pattern& P, const std::vector<uint8_t>& active, int 
         // rows are one range (the compact cycle on a split level)
         const bool om1 = dist && l + 1 <= n_dist && l + 1 < (int)own.size();
         prt = sort_perm(key, om1 ? &own[l + 1] : nullptr, world, om1 ? &out.rt_own : nullptr,
-                        spatial ? &bases[l + 1] : nullptr);
+                        spatial ? &bases[l + 1] : nullptr, l == 0 ? win0 : kAmgSortWindow);
       }
       if (!(err = layout(RT, prt, &perm[l], out.RT, eRT)).empty()) return err;
       out.rt_row.assign(L.nc, 0);
@@ -805,6 +807,78 @@ std::string build_amg_halo(const Pattern& P, const std::vector<uint8_t>& active,
     }
     halo.gptr[i + 1] = (int32_t)halo.gslot.size();
   }
+  return "";
+}
+
+// The block halo plan of level 0 (amg.hpp AmgFusePlan).
+std::string build_amg_fuse(const AmgPlan& plan, int64_t halo_cap, AmgFusePlan& out) {
+  out = AmgFusePlan();
+  auto off = [&](const char* why) {
+    out.on = false;
+    out.why = why;
+    out.hptr.clear();
+    out.hrow.clear();
+    out.hpt.clear();
+    out.lcol.clear();
+    return std::string();
+  };
+  if (plan.world != 1 || plan.n_dist != 0) return off("a split plan");
+  if (plan.lev.size() < 2) return off("one level");
+  const AmgLevel& L = plan.lev[0];
+  const SellPat& A = L.A;
+  const int64_t n = A.n, B = plan.l0_window;
+  if (n <= 0 || L.PT.n != n || (int64_t)L.pt_row.size() != n) return off("no compact transfer on level 0");
+  if (B < 64 || B % 64) return off("the block is no multiple of 64 rows");
+  out.B = B;
+  out.n_blocks = (n + B - 1) / B;
+  // P̃_0's rows of block b are the level's rows of block b (aligned windows)
+  std::vector<int32_t> inv(n, -1);
+  for (int64_t a = 0; a < n; ++a) {
+    const int64_t i = L.pt_row[a];
+    if (i < 0 || i >= n || i / B != a / B) return off("P̃_0's labelling leaves the level-0 blocks");
+    inv[i] = (int32_t)a;
+  }
+  out.hptr.assign(out.n_blocks + 1, 0);
+  out.lcol.assign(A.col.size(), (uint16_t)0xFFFF);
+  std::vector<int32_t> halo;
+  for (int64_t b = 0; b < out.n_blocks; ++b) {
+    const int64_t lo = b * B, hi = std::min(n, lo + B);
+    halo.clear();
+    for (int64_t r = lo; r < hi; ++r)
+      for (int k = 0; k < A.rlen[r]; ++k) {
+        const int32_t j = A.col[A.pos(r, k)];
+        if (j < 0) continue;
+        if (j != r) ++out.offdiag;
+        if (j >= lo && j < hi) continue;
+        ++out.cut;
+        halo.push_back(j);
+      }
+    std::sort(halo.begin(), halo.end());
+    halo.erase(std::unique(halo.begin(), halo.end()), halo.end());
+    const int64_t nh = (int64_t)halo.size();
+    out.max_halo = std::max(out.max_halo, nh);
+    if (nh > halo_cap || B + nh > 32767) {
+      off("a block's halo exceeds the capacity");
+      out.B = B;
+      out.n_blocks = (n + B - 1) / B;
+      out.max_halo = nh;
+      return "";
+    }
+    for (int64_t r = lo; r < hi; ++r)
+      for (int k = 0; k < A.rlen[r]; ++k) {
+        const int64_t q = A.pos(r, k);
+        const int32_t j = A.col[q];
+        if (j < 0) continue;
+        if (j >= lo && j < hi) out.lcol[q] = (uint16_t)(j - lo);
+        else out.lcol[q] = (uint16_t)(B + (std::lower_bound(halo.begin(), halo.end(), j) - halo.begin()));
+      }
+    for (const int32_t j : halo) {
+      out.hrow.push_back(j);
+      out.hpt.push_back(inv[j]);
+    }
+    out.hptr[b + 1] = (int32_t)out.hrow.size();
+  }
+  out.on = true;
   return "";
 }
 

@@ -200,6 +200,10 @@ struct Part {
   // amg_kernels.hpp AmgPx); null: partitioned or a one-level plan
   float* amg_uh = nullptr;
   int64_t amg_uh_stride = 0;
+  // level 0's block halo plan (option amg_fuse_l0, amg.hpp AmgFusePlan): the
+  // last up sweep and w = A u in one launch (amg.hip k_amg_up_w) while on
+  AmgFusePlan amg_fplan;
+  AmgFuseD amg_fuse;
   // the plan's preconditioner kind: MFEA_PC_GAMG (the hierarchy) or a
   // one-level plan with multicolour sweeps (MFEA_PC_SOR / MFEA_PC_ICC, sweep.hip)
   int amg_kind = MFEA_PC_GAMG;
@@ -437,6 +441,12 @@ struct mfea_handle {
   int64_t opt_amg_collapse_pairs = 8000000;  // … budget: its setup products' list items
   int opt_amg_spatial = -1;  // GAMG: rows labelled in Z-order (1), depth-first (0), by locality (-1)
   int opt_amg_up_lanes = 0;  // GAMG compact up sweep: lanes per P̃ row (0: by width)
+  // GAMG: level 0's last up sweep and w = A u as one launch over block-local
+  // rows (k_amg_up_w): -1 by kAmgFuseAuto, 0 never, 1 where
+  // the plan allows it.  amg_l0_window: level 0's sorting window in rows
+  // (0: kAmgFuseWindow where the fusion is wanted, 4096 elsewhere)
+  int opt_amg_fuse_l0 = -1;
+  int64_t opt_amg_l0_window = 0;
   // GAMG: ρ̂ of the levels below 0 in ppm (ω_l = 4 / (3 ρ̂)); 0: max(2, g_l / 1.45), the
   // Gershgorin-safe value.  A solve that fails with it falls back to the safe
   // value for the handle's lifetime (amg_safe_omega, omega_fallback).
@@ -1510,6 +1520,22 @@ static int amg_w_k(const AmgPlan& pl) {
 constexpr int kAmgCollapseAutoLevel = 2;
 constexpr int64_t kMergeRows = 131072;  // amg_merge -1: level-0 rows up to which levels 0 and 1 merge
 
+// Level 0's up sweep and w = A u in one launch (option amg_fuse_l0; DESIGN.md
+// §4.12): what −1 means, and the level-0 window the fused plans are built at
+constexpr bool kAmgFuseAuto = true;
+constexpr int64_t kAmgFuseWindow = 1408;
+bool amg_fuse_opted(const mfea_handle* h) { return h->opt_amg_fuse_l0 > 0 || (h->opt_amg_fuse_l0 < 0 && kAmgFuseAuto); }
+// … wanted for a plan still to be built: one partition, GAMG's compact cycle,
+// and not a network whose levels 0 and 1 merge (those keep their launches)
+bool amg_fuse_wanted(const mfea_handle* h, const Part& pt, int kind) {
+  if (!amg_fuse_opted(h) || partitioned(h) || kind != MFEA_PC_GAMG || h->opt_amg_cycle != 1) return false;
+  return !(h->opt_amg_merge > 0 || (h->opt_amg_merge < 0 && pt.P.n_free <= kMergeRows));
+}
+int64_t amg_l0_window(const mfea_handle* h, const Part& pt, int kind) {
+  if (h->opt_amg_l0_window > 0) return h->opt_amg_l0_window;
+  return amg_fuse_wanted(h, pt, kind) ? kAmgFuseWindow : kAmgSortWindow;
+}
+
 // ρ̂ of the levels below 0 (0: the Gershgorin rule), until a solve has failed
 // with it
 double coarse_rho(const mfea_handle* h) {
@@ -1618,6 +1644,20 @@ int upload_amg(mfea_handle* h, Part& pt, const AmgPlan& pl, const AmgRank* rk = 
       (h->opt_amg_merge > 0 || pl.lev[0].A.n <= kMergeRows)) {
     const std::string merr = build_amg_merge(pl, pt.amg_coll, pt.amg_mplan);
     if (!merr.empty()) return fail(MFEA_EINVAL, merr);
+  }
+  // level 0 in tiles of its sorting window (AmgCg::w_tile) and the block halo
+  // plan over them: one partition's GAMG hierarchy whose window is a tile size
+  pt.amg_fplan = AmgFusePlan();
+  const bool tiled = !rk && !partitioned(h) && pt.amg_kind == MFEA_PC_GAMG && nlev >= 2 &&
+                     pl.l0_window != kAmgSortWindow && amg_fuse_tile_ok(pl.l0_window);
+  if (tiled && amg_fuse_opted(h)) {
+    const std::string ferr = build_amg_fuse(pl, amg_fuse_halo_cap(nd, pl.l0_window), pt.amg_fplan);
+    if (!ferr.empty()) return fail(MFEA_EINVAL, ferr);
+  }
+  std::vector<int32_t> lcol2;  // the local columns, two to a word
+  if (pt.amg_fplan.on) {
+    lcol2.assign((pt.amg_fplan.lcol.size() + 1) / 2, 0);
+    std::memcpy(lcol2.data(), pt.amg_fplan.lcol.data(), pt.amg_fplan.lcol.size() * sizeof(uint16_t));
   }
   // the level-0 label of every free row (the floating mask's scatter, launch_floating)
   std::vector<int32_t> row0_inv;
@@ -1799,6 +1839,18 @@ int upload_amg(mfea_handle* h, Part& pt, const AmgPlan& pl, const AmgRank* rk = 
     pt.amg_cg.u = F((size_t)nd * nf);
     pt.amg_uh_stride = (int64_t)amg_al((size_t)nd * nf);
     pt.amg_uh = !rk && nlev > 1 ? F((size_t)kAmgPxSlots * pt.amg_uh_stride) : nullptr;
+    pt.amg_cg.w_tile = tiled ? (int)pl.l0_window : 0;
+    pt.amg_cg.skip_up0 = 0;
+    pt.amg_fuse = AmgFuseD{};
+    if (pt.amg_fplan.on) {
+      const AmgFusePlan& fp = pt.amg_fplan;
+      pt.amg_fuse.on = 1;
+      pt.amg_fuse.hcap = (int)std::max<int64_t>(64, (fp.max_halo + 63) / 64 * 64);
+      pt.amg_fuse.hptr = I(fp.hptr);
+      pt.amg_fuse.hrow = I(fp.hrow);
+      pt.amg_fuse.hpt = I(fp.hpt);
+      pt.amg_fuse.lcol = reinterpret_cast<const int16_t*>(I(lcol2));
+    }
     // the merged levels' operators, lists and vector buffer
     pt.amg_mg = AmgMergeD{};
     if (pt.amg_mplan.on) {
@@ -2008,6 +2060,30 @@ AmgPx px_of(const Part& pt, int k0, int cnt) {
   px.cnt = cnt;
   return px;
 }
+// Level 0's up sweep and w = A u as one launch (k_amg_up_w): the plan's halo
+// fits (upload_amg) and the cycle run now is the compact, unmerged one with
+// one lane per P̃_0 row — the merged cycle, the four-step cycle, the sweeps
+// and the partitioned solves keep their launches
+bool amg_fused(const mfea_handle* h, const Part& pt) {
+  return amg_fuse_opted(h) && pt.amg_fuse.on && pt.amg_cg.w_tile > 0 && !pt.amg_cg.sweep && !pt.amg_mg.on &&
+         pt.amg_cg.cycle == 1 && amg_compact_ok(pt.amg_lev.data(), (int)pt.amg_lev.size(), 0) &&
+         amg_up_lanes(pt.amg_lev[0]) == 1;
+}
+// the V-cycle up to level 0's up sweep, then that sweep and w = A u; or the
+// V-cycle and w = A u
+void launch_vcycle_w(mfea_handle* h, Part& pt, int j, bool first, const AmgCg& cg) {
+  hipStream_t s = h->stream;
+  if (amg_fused(h, pt)) {
+    AmgCg c = cg;
+    c.skip_up0 = 1;
+    launch_precond(h, pt, nullptr, &c);
+    launch_amg_up_w(s, pt.amg.nd, j, first, pt.amg_lev[0], pt.amg_lev[1], cg, pt.amg_fuse, pt.slots.ptr,
+                    pt.cg_part.ptr);
+  } else {
+    launch_precond(h, pt, nullptr, &cg);
+    launch_amg_cg_w(s, pt.amg.nd, j, first, pt.amg_lev[0], cg, pt.slots.ptr, pt.cg_part.ptr);
+  }
+}
 // replay launches of a chunk of `chunk` groups (enqueue_amg_chunk)
 int px_replays(int chunk) { return 1 + (chunk > 0 ? (chunk - 1) / (kAmgPxSlots - 1) : 0); }
 
@@ -2094,6 +2170,7 @@ int ensure_amg(mfea_handle* h, Part& pt, bool* rebuilt, int kind = MFEA_PC_GAMG)
   AmgLayout lay;
   lay.spatial = h->opt_amg_spatial;
   lay.by_a = h->opt_amg_cycle == 1;
+  lay.l0_window = amg_l0_window(h, pt, kind);
   const bool sweep = kind == MFEA_PC_SOR || kind == MFEA_PC_ICC;
   std::string err = build_amg(pt.P, key, lane_dofs(h), pt.amg, sweep ? 1 : h->opt_amg_max_levels, nullptr,
                               amg_strength(h), lay);
@@ -2133,9 +2210,7 @@ void enqueue_amg_iteration(mfea_handle* h, Part& pt, int j, bool profile) {
   const bool lazy = amg_lazy(h, pt);
   const AmgCg cg = lazy ? px_cg(pt, j) : pt.amg_cg;
   launch_amg_cg_update(s, nd, j, L0, cg, pt.slots.ptr, pt.state.ptr, pt.cg_part.ptr, nullptr, lazy);
-  (void)profile;
-  launch_precond(h, pt, nullptr, &cg);
-  launch_amg_cg_w(s, nd, j, profile, L0, cg, pt.slots.ptr, pt.cg_part.ptr);
+  launch_vcycle_w(h, pt, j, profile, cg);
 }
 
 // ---- partitioned GAMG exchanges -------------------------------------------
@@ -2278,8 +2353,7 @@ void enqueue_amg_chunk(mfea_handle* h, Part& pt, int chunk, bool close) {
   int k0 = 0;
   for (int j = 0; j < chunk; ++j) {
     const AmgCg cg = lazy ? px_cg(pt, j + 1) : pt.amg_cg;
-    launch_precond(h, pt, nullptr, &cg);
-    launch_amg_cg_w(s, nd, j, false, L0, cg, pt.slots.ptr, pt.cg_part.ptr);
+    launch_vcycle_w(h, pt, j, false, cg);
     launch_amg_cg_update(s, nd, j + 1, L0, cg, pt.slots.ptr, pt.state.ptr, pt.cg_part.ptr, nullptr, lazy);
     if (lazy && (j + 1) % (kAmgPxSlots - 1) == 0 && j + 1 < chunk) {
       launch_amg_px_replay(s, nd, pt.amg_cg, pt.slots.ptr, px_of(pt, k0, j + 2 - k0));
@@ -2343,8 +2417,7 @@ void enqueue_amg_entry(mfea_handle* h, Part& pt, bool skip_init = false) {
   if (!skip_init) launch_amg_cg_init(s, nd, L0, pt.amg_cg, cg_vecs(pt).r[0]);
   const bool lazy = amg_lazy(h, pt);  // (update 0's u in slot 0: the first chunk's replay applies it)
   const AmgCg cg = lazy ? px_cg(pt, 0) : pt.amg_cg;
-  launch_precond(h, pt, nullptr, &cg);
-  launch_amg_cg_w(s, nd, 0, true, L0, cg, pt.slots.ptr, pt.cg_part.ptr);
+  launch_vcycle_w(h, pt, 0, true, cg);
   launch_amg_cg_update(s, nd, 0, L0, cg, pt.slots.ptr, pt.state.ptr, pt.cg_part.ptr, nullptr, lazy);  // update 0
 }
 
@@ -2392,6 +2465,11 @@ uint64_t amg_setup_key(mfea_handle* h, Part& pt, double reg) {
   const int ints[5] = {pt.amg.nd, h->opt_amg_fuse_setup, pt.amg_cg.cycle, pt.amg_cg.coll, pt.amg_cg.sweep};
   k = fnv1a(k, &pt.swd, sizeof pt.swd);
   k = fnv1a(k, ints, sizeof ints);
+  // (the entry's launches: fused or not, the tiles, the halo plan's arrays)
+  const int64_t fz[3] = {amg_fused(h, pt) ? 1 : 0, pt.amg_cg.w_tile, pt.amg_fuse.hcap};
+  const void* fptrs[4] = {pt.amg_fuse.hptr, pt.amg_fuse.hrow, pt.amg_fuse.hpt, pt.amg_fuse.lcol};
+  k = fnv1a(k, fz, sizeof fz);
+  k = fnv1a(k, fptrs, sizeof fptrs);
   k = fnv1a(k, &reg, sizeof reg);
   return k;
 }
@@ -5070,6 +5148,17 @@ int mfea_set_option(mfea_handle* h, const char* name, int64_t value) {
     h->opt_amg_spatial = (int)value;
     rebuild = true;
   }
+  else if (n == "amg_fuse_l0") {
+    if (value < -1 || value > 1) return fail(MFEA_EINVAL, "amg_fuse_l0: -1 (auto), 0 or 1");
+    h->opt_amg_fuse_l0 = (int)value;
+    rebuild = true;  // (auto also picks level 0's window)
+  }
+  else if (n == "amg_l0_window") {
+    if (value < 0 || value % 64 || value > (int64_t(1) << 30))
+      return fail(MFEA_EINVAL, "amg_l0_window: 0 (auto) or a multiple of 64 rows");
+    h->opt_amg_l0_window = value;
+    rebuild = true;
+  }
   else if (n == "amg_up_lanes") {
     if (value != 0 && value != 1 && value != 2 && value != 4)
       return fail(MFEA_EINVAL, "amg_up_lanes: 0 (by width), 1, 2 or 4");
@@ -5387,6 +5476,15 @@ int mfea_get_option(mfea_handle* h, const char* name, int64_t* value) {
   else if (n == "sweep_colors") *value = part0(h).sweep.colors;  // read-only
   else if (n == "sweep_pieces") *value = part0(h).sweep.n_pieces;  // read-only
   else if (n == "amg_up_lanes") *value = h->opt_amg_up_lanes;
+  else if (n == "amg_fuse_l0") *value = h->opt_amg_fuse_l0;
+  else if (n == "amg_l0_window") *value = h->opt_amg_l0_window;
+  // read-only, partition 0's plan: the fused launch is in use; level 0's
+  // window; the largest block halo and the capacity it was held against
+  else if (n == "amg_fused_l0") *value = !h->parts.empty() && amg_fused(h, *h->parts[0]) ? 1 : 0;
+  else if (n == "amg_l0_window_used") *value = h->parts.empty() ? 0 : h->parts[0]->amg.l0_window;
+  else if (n == "amg_fuse_max_halo") *value = h->parts.empty() ? 0 : h->parts[0]->amg_fplan.max_halo;
+  else if (n == "amg_fuse_halo_cap")
+    *value = h->parts.empty() ? 0 : amg_fuse_halo_cap(h->parts[0]->amg.nd, h->parts[0]->amg.l0_window);
   else if (n == "amg_coarse_rho_ppm") *value = h->opt_amg_coarse_rho_ppm;
   else if (n == "amg_a0_slot") *value = h->opt_amg_a0_slot;
   else if (n == "amg_safe_omega") *value = h->amg_safe_omega ? 1 : 0;  // read-only

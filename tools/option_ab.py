@@ -33,6 +33,9 @@ def child(a, value):
     xyz, e2n = synth.tiled_mesh(nx, ny, chords=a.config.startswith("C5"))
     top, bot = synth.grips(xyz)
     eng = Engine(0)
+    for kv in a.set:  # options held fixed in both legs
+        k, v = kv.split("=")
+        eng.set_option(k, int(v))
     eng.set_option(a.option, value)
     eng.set_material(fs.E_mod, fs.A, fs.I)
     eng.set_mesh(xyz, e2n)
@@ -65,6 +68,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=10)
     ap.add_argument("--child", type=int, default=None)
+    ap.add_argument("--set", nargs="*", default=[], help="other options name=value, the same in every leg")
     a = ap.parse_args()
     if a.child is not None:
         child(a, a.child)
@@ -73,7 +77,8 @@ def main():
     for rnd in range(a.rounds):
         for v in a.values:
             out = subprocess.run([sys.executable, __file__, "--option", a.option, "--config", a.config,
-                                  "--steps", str(a.steps), "--warmup", str(a.warmup), "--child", str(v)],
+                                  "--steps", str(a.steps), "--warmup", str(a.warmup), "--child", str(v),
+                                  "--set", *a.set],
                                  capture_output=True, text=True, timeout=300)
             if out.returncode != 0:
                 print(json.dumps({"option": a.option, "value": v, "rc": out.returncode,
