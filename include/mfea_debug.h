@@ -39,6 +39,8 @@ int mfea_debug_floating(mfea_handle* h, uint8_t* out);
  * measured best; the library reads no environment variables).  Names:
  *   "graph" 0|1          single-partition CG chunks as hipGraph replays (1)
  *   "dist_graph" 0|1     partitioned chunks, exchanges included, likewise (1)
+ *   "phase_times" 0|1    record the phase events, mfea_stats t_*_ms (0: each event between two
+ *                        kernels leaves the GPU idle for 5–10 µs)
  *   "order" -1|0|k       free-row order: DFS (-1), natural (0), degree sort in windows of k
  *   "lane_dof" 0|3       planar meshes on 2 DOFs per node (0) or 3
  *   "cg_kernel" 0|1|2    Jacobi CG kernel: by density (0), lanes (1), SELL (2)
@@ -47,8 +49,15 @@ int mfea_debug_floating(mfea_handle* h, uint8_t* out);
  *   "ell_compact" 0|1    lane kernels: compact halo records (1)
  *   "amg_tail_rows" n    GAMG: deep levels of ≤ n rows in one workgroup (2048; 0 off)
  *   "amg_tail_lds" 0|1   GAMG: the tail's vectors in LDS (1) or global memory (0)
- *   "amg_restrict_lanes" 0|1|2|4|8  GAMG: lanes per coarse row of the restriction (0: by width)
+ *   "amg_restrict_lanes" 0|1|2|4|8|16  GAMG: lanes per coarse row of the restriction (0: by
+ *                        width; 16: the compact down sweep)
  *   "amg_op_lanes" 0|1|2|4        GAMG: lanes per row of the operators below level 0 (0: by width)
+ *   "amg_v_lanes" 0|1|2|4|8|16    GAMG collapsed cycle: lanes per V row (0: by width)
+ *   "amg_small_lanes" n  GAMG: wide rows of small levels at 16 lanes below this many threads
+ *                        (65536; 0 .. 2^30)
+ *   "amg_merge" -1|0|1   GAMG: levels 0 and 1 merged around a level-2 collapse: small
+ *                        networks (-1), off, on.  Read-only "amg_merged": the plan's form
+ *   "amg_down_split" 0|1 GAMG compact down sweep: R̂ and Ã rows as two launches (0; experiment)
  *   "dist_timeout_ms" n  RCCL waits: give up after n ms
  *   "part_slack_pct" n   partition boundaries move ≤ n % of a strip to the
  *                        fewest crossing elements (35; 0 = equal free-node counts)
@@ -116,9 +125,9 @@ int mfea_debug_floating(mfea_handle* h, uint8_t* out);
  *   "keep_operator" 0|1  mfea_step, one partition: keep K while the active set, the material,
  *                        the build and asm_kernel hold (only the RHS is formed), and keep the
  *                        GAMG hierarchy's values while K, the plan, the floating mask, reg
- *                        and ω hold (1; 0: assemble and set up every step).  Every other
- *                        option set drops both, but phase_times, run_register, amg_close, amg_start,
- *                        amg_lazy_px and amg_big_chunk.
+ *                        and ω hold (1; 0: assemble and set up every step).  Setting
+ *                        any option drops both, but those that mfea_debug_option_info
+ *                        reports with MFEA_OPT_KEEPS_KEPT (and keep_operator itself, set to 1).
  *                        Read-only totals since mfea_create: "op_kept_steps" (steps that
  *                        skipped the assembly), "amg_setup_kept" (solves that skipped the
  *                        numeric setup) — mfea.h mfea_step, DESIGN.md §4.7
@@ -182,6 +191,20 @@ int mfea_set_option(mfea_handle* h, const char* name, int64_t value);
  * option "amg_dist" names, or with "amg_dist" -1 the one picked for the
  * current active set (0 block Jacobi, 1 global hierarchy, -1 not yet). */
 int mfea_get_option(mfea_handle* h, const char* name, int64_t* value);
+
+/* The options by index, without a handle: the writable ones in the order of
+ * the library's table, then the read-only names.  *name: the option's name;
+ * *dflt: its default (0 for a read-only name); *flags: MFEA_OPT_* bits.
+ * MFEA_EINVAL past the end. */
+#define MFEA_OPT_WRITABLE 1        /* mfea_set_option takes it */
+#define MFEA_OPT_REBUILDS_LAYOUT 2 /* setting it rebuilds the symbolic layout at the next call */
+#define MFEA_OPT_KEEPS_KEPT 4      /* setting it keeps K and the hierarchy's values (keep_operator) */
+int mfea_debug_option_info(int index, const char** name, int64_t* dflt, int* flags);
+
+/* What mfea_set_option(h, name, value) would do, without a handle: 0 and in
+ * *stored the value mfea_get_option would then read back, or MFEA_EINVAL (an
+ * unknown or read-only name, a value outside the option's legal ones). */
+int mfea_debug_option_check(const char* name, int64_t value, int64_t* stored);
 
 /* The MFEA_PC_GAMG hierarchy for the current active set (built if needed;
  * partitioned handles: the global hierarchy of option "amg_dist" 1):

@@ -1859,7 +1859,7 @@ static dim3 rows_grid(int64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBl
 // rows (C3: 438 blocks, one pass; same-box A/B of the whole iteration 166.6
 // vs 170.0 µs at 512 and 169.5 at 1024; C5 1786 vs 1831 vs 1784), 512 / 256
 // below.  Both read the w kernel's partial count, amg_w_grid.  cg.w_block > 0
-// overrides the choice (mfea_set_option "amg_w_block").
+// overrides the choice (capi.hip kAmgWBlock).
 // Round 4: between 512·512 and 768·512 rows the smallest of 576 / 640 / 704 /
 // 768 whose grid fits kCgMaxG blocks in one pass — at C3 704 × 478 blocks
 // instead of 768 × 438: two blocks on every CU carry 1,408 rows instead of

@@ -24,6 +24,7 @@
 #include "kernels.hpp"
 #include "mfea_debug.h"
 #include "mfea.h"
+#include "options.hpp"
 #include "partition.hpp"
 #include "records.hpp"
 #include "run.hpp"
@@ -256,7 +257,8 @@ struct MatKey {
   bool operator!=(const MatKey& o) const { return !(*this == o); }
 };
 
-struct mfea_handle {
+// (the tuning options and their defaults: Options, options.hpp)
+struct mfea_handle : Options {
   int device = 0;
   hipStream_t stream = nullptr;
   double E = 2500.0, A = 0.0, I = 0.0;
@@ -292,7 +294,6 @@ struct mfea_handle {
   int nparts = 1, axis = -1;
   int world = 1, rank = 0;
   ncclComm_t comm = nullptr;
-  double dist_timeout_s = 60.0;  // per wait; option "dist_timeout_ms"
   SolveState* h_state = nullptr;       // pinned, 2 entries
   SolveState* d_host_state = nullptr;  // device view of h_state (mapped)
   double* h_red = nullptr;             // pinned
@@ -326,45 +327,12 @@ struct mfea_handle {
   uint64_t graph_setup_key[2] = {};
   hipEvent_t ev[6] = {};
   hipEvent_t ev_setup = nullptr;
-  // option "phase_times": record the phase events (mfea_stats t_*_ms).  Off by
-  // default: each event recorded between two kernels left the GPU idle for
-  // ≈ 5–10 µs (C2 step 0.771 → 0.737 ms, C3 1.665 → 1.635 without them)
-  bool opt_phase_times = false;
   bool ev_setup_used = false;  // the last solve recorded ev_setup (GAMG)
   bool in_step = false;        // mfea_step: the solve's end is waited for by post
   // mfea_step's assembly also formed the GAMG solves' RHS for these grip
   // displacements (AsmRhs); the next solve_amg uses it instead of k_amg_rhs
   bool rhs_fused = false;
   double rhs_dy[2] = {0.0, 0.0};
-  // mfea_step, one partition (option "spec_post"): the post kernels and
-  // their read-back are enqueued behind the solve's planned batch, before the
-  // host waits for it, so the one wait covers both — one host round trip per
-  // step instead of two.  spec_on: this step may; spec_launched: enqueued
-  // behind the last batch (undone by k_unfail when the solve goes on)
-  int opt_spec_post = 1;
-  // the solve's entry launches (cg_init, first V-cycle, w, update 0) in the
-  // captured setup graph (option "setup_entry")
-  int opt_setup_entry = 1;
-  // mfea_step, one partition, GAMG / SOR / ICC, graphs on, no phase events:
-  // the planned batch, the finish and the post as one captured graph
-  int opt_batch_graph = 1;
-  // mfea_step likewise: the assembly with the fused RHS and the CG start
-  // captured at the head of the setup graph, the grip displacements read from
-  // pinned h_red[14..15] by a copy node (option "step_graph").  Off: measured
-  // 13 µs slower per step at C2 and C3 (profiles/r6/ab_step_graph_wall.log) —
-  // an eager assembly runs while the host checks the plan and the setup
-  // graph's key; deferred, the GPU waits for that host work
-  int opt_step_graph = 0;
-  int opt_graph_start = 1;  // the CG start (k_cg_init_finalize) at the setup graph's head
-  // with batch_graph: the batch, finish and post behind the setup in one graph
-  int opt_combo_graph = 1;
-  // One partition (option "keep_operator"): mfea_step keeps K
-  // (val / diag) while what it was assembled from holds — the activity
-  // (act_gen), the material, the build (`assembled`), the assembly kernel —
-  // and solve_amg keeps the numeric setup's values while K (op_gen) and the
-  // setup's other inputs hold (Part::kept).  None of them depends on the grip
-  // displacements, the only thing that moves from one load step to the next.
-  int opt_keep_operator = 1;
   int64_t op_gen = 0;  // bumped by every launch that writes val / diag
   struct {
     bool ok = false;
@@ -375,20 +343,9 @@ struct mfea_handle {
   int last_precond = -1;          // the last solve's preconditioner kind
   int64_t op_kept_steps = 0;      // read-only option: steps that skipped the assembly
   int64_t amg_setup_kept = 0;     // read-only option: solves that skipped the numeric setup
-  // One-partition GAMG solves on the unpreconditioned norm end every chunk
-  // with a closing check (enqueue_amg_chunk): the planned batch is one group
-  // shorter, the converging update's V-cycle and w = A u are not run.  0: the
-  // batch ends with the update that finds the convergence, as before.
-  int opt_amg_close = 1;
   int64_t amg_close_hits = 0;     // read-only option: solves that ended at the closing check
   int amg_last_cycles = 0;        // read-only option: preconditioner applications the last GAMG solve queued
-  // A solve on kept hierarchy values starts with ONE launch (k_amg_start: the
-  // RHS, the CG's state and level-0 b) instead of three.  0: the three.
-  int opt_amg_start = 1;
   int64_t amg_start_fused = 0;    // read-only option: solves that started with k_amg_start
-  // The update moves s, r and level 0's x only; p and x are replayed from the
-  // chunk's kept u at its end (amg_kernels.hpp AmgPx).  0: the fat update.
-  int opt_amg_lazy_px = 1;
   int64_t amg_px_replays = 0;     // read-only option: replay launches queued by the solves
   bool setup_skipped = false;     // the last solve did (phase times: t_setup_ms = 0)
   MatKey graph_batch_mat{};       // the material / properties graph_batch's post kernels were captured with
@@ -406,7 +363,6 @@ struct mfea_handle {
   bool ev_on = false;
   double ev_strain = 0.0, ev_tie = 0.0, ev_lam_max = 0.0;
   int32_t ev_index = 0;
-  int opt_event_scratch = 1;  // option "event_scratch": 1 the scan keeps ε_e for the apply, 0 it forms them again
   hipEvent_t poll[2] = {};
   int64_t n_active = 0;
   bool act_all = false;  // every element is active on the device (set_active(NULL), no failure since)
@@ -416,79 +372,7 @@ struct mfea_handle {
   std::vector<uint8_t> act_host;
   bool act_host_ok = false;
   int64_t act_count = 0;
-  // tuning options (mfea_set_option; defaults from the environment at create)
-  bool opt_graph = true;       // single-partition chunks replay as hipGraphs
-  bool opt_dist_graph = true;  // partitioned chunks too
-  int opt_order = kOrderDFS;   // free-row order (symbolic.hpp)
-  int opt_lane_dof = 0;        // 0: 2 DOFs per node on planar meshes, 3: always 3
-  int opt_cg_kernel = 0;       // Jacobi CG: 0 by density, 1 lanes, 2 SELL
-  int opt_ell_block = 256;     // lane kernels: threads per block
-  int64_t opt_ell_maxg = 0;    // lane kernels: grid cap (0: kCgMaxG)
-  bool opt_ell_compact = true; // lane kernels: compact halo records
-  int64_t opt_amg_tail_rows = 2048;  // GAMG: levels of at most this many rows run in one workgroup
-  int opt_amg_max_levels = kAmgMaxLevels;  // GAMG: hierarchy depth cap
-  int opt_amg_w_block = 0;     // GAMG: w = A u threads per block (0: by size)
-  int opt_amg_rlanes = 0;      // GAMG: restriction lanes per coarse row (0: by width)
-  int opt_amg_down_split = 0;  // GAMG compact down sweep: R̂ and Ã rows as two launches (experiment)
-  int opt_amg_merge = -1;      // GAMG: levels 0 and 1 merged around a level-2 collapse (-1: small networks, 0 off, 1 on)
-  int opt_amg_v_lanes = 0;     // GAMG collapsed cycle: lanes per V row (0: by width; 1, 2, 4, 8, 16)
-  int64_t opt_amg_small_lanes = 65536;  // GAMG: wide rows of small levels at 16 lanes below this many threads
-  int opt_amg_alanes = 0;      // GAMG: operator lanes per row below level 0 (0: by width)
-  int opt_amg_tail_lds = 1;    // GAMG: the single-workgroup tail keeps its vectors in LDS
-  int opt_amg_collapse = -1;           // GAMG: collapse the compact cycle below the highest level
-                                      // within budget (-1), never (0), or from level ≥ k (k ≥ 1)
-  int64_t opt_amg_collapse_mb = 32;     // … budget: the collapsed operator's bytes
-  int64_t opt_amg_collapse_pairs = 8000000;  // … budget: its setup products' list items
-  int opt_amg_spatial = -1;  // GAMG: rows labelled in Z-order (1), depth-first (0), by locality (-1)
-  int opt_amg_up_lanes = 0;  // GAMG compact up sweep: lanes per P̃ row (0: by width)
-  // GAMG: level 0's last up sweep and w = A u as one launch over block-local
-  // rows (k_amg_up_w): -1 by kAmgFuseAuto, 0 never, 1 where
-  // the plan allows it.  amg_l0_window: level 0's sorting window in rows
-  // (0: kAmgFuseWindow where the fusion is wanted, 4096 elsewhere)
-  int opt_amg_fuse_l0 = -1;
-  int64_t opt_amg_l0_window = 0;
-  // GAMG: ρ̂ of the levels below 0 in ppm (ω_l = 4 / (3 ρ̂)); 0: max(2, g_l / 1.45), the
-  // Gershgorin-safe value.  A solve that fails with it falls back to the safe
-  // value for the handle's lifetime (amg_safe_omega, omega_fallback).
-  int64_t opt_amg_coarse_rho_ppm = 1750000;
-  int opt_amg_a0_slot = 1;  // level 0's blocks one thread per position (k_amg_a0slot) at a fixed ω
-  bool amg_safe_omega = false;
-  int64_t opt_amg_x1_rows = 2048;  // GAMG setup: levels of at most this many rows run on one XCD (0: never;
-                                   // C3: levels 4-5 gain 1-2 µs per launch, level 3 at 8192 lost as much)
-  int opt_amg_big_chunk = 8;  // GAMG: iterations per chunk of a planned batch (drive_sized)
-  int opt_sweep_piece = kSweepPieceLen;  // SOR / ICC: rows per chain piece (amg.hpp SweepPlan)
-  int opt_amg_fuse_setup = 1;  // GAMG setup: the compact operators fused into the Galerkin chain's launches
-  int64_t opt_amg_theta_ppm = 0;  // GAMG: strength threshold θ·10⁶ of the level-0 aggregation (0: all strong)
-  int opt_amg_cycle = 1;       // GAMG: 1 the compact V-cycle (two sweeps per level), 0 four steps
-  double opt_part_slack = 0.35;  // partition boundaries: min-cut search window (fraction of a strip)
-  // GAMG over element failures: 1 keep the hierarchy (floating pieces masked)
-  // until a solve needs more than amg_rebuild_pct % of the iterations of the
-  // hierarchy's first solve (+2), then rebuild; 0 rebuild on every new active set
-  int opt_amg_reuse = 1;
-  // assembly: 0 row gather (one launch, fused GAMG RHS), 1 element colours
-  // (a launch per colour), 2 element pass + row pass (two launches)
-  int opt_asm_kernel = 0;
-  int opt_cc_tile = 1024;  // floating rows on the device: rows per LDS tile (512, 1024, 2048, 4096; C3 73 µs at 512-1024, C5 0.6 ms at 1024-2048)
-  int opt_amg_rebuild_pct = 800;
-  // ... or once the time its solves spent on iterations above that count
-  // reaches this % of the time the last build took (0: off).  Rent-or-buy:
-  // a C5 rebuild costs 2.4 s of host work — ≈ 80 steps — so a kept hierarchy
-  // that needs 40-100 % more iterations is kept; at most twice the cost of
-  // the best choice in hindsight (measured)
-  int opt_amg_rebuild_rent = 100;
-  int opt_amg_dist = -1;          // partitioned GAMG: 1 the global hierarchy (distributed V-cycle), 0 block
-                                  // Jacobi over per-partition hierarchies, -1 whichever solves faster (measured)
-  int64_t opt_amg_rep_rows = 32768;  // distributed V-cycle: levels of at most this many rows are replicated
-  // distributed V-cycle: 1 the compact cycle with level 0 split and every
-  // level below replicated (x_0 halo, x_1 all-gather, u halo: three exchange
-  // points per iteration), 0 the four-step cycle over the levels of more than
-  // amg_rep_rows rows (four exchange points per split level)
-  int opt_amg_dist_cycle = 1;
-  // GAMG over RCCL: the CG's per-rank partial sums as ONE ncclAllReduce of
-  // [world][4] doubles, every rank's buffer zero but its own row (1; the sum
-  // is then each row exactly, summed by every rank in rank order as before),
-  // or as world − 1 send / receive pairs per rank (0)
-  int opt_dist_sums = 1;
+  bool amg_safe_omega = false;  // read-only option: a solve failed at amg_coarse_rho_ppm; ω is the safe value
   // distributed GAMG (partitioned handles, option "amg_dist" 1): the whole
   // mesh's pattern and node owners (built with the partitions), and ONE
   // global hierarchy for the current global element activity
@@ -525,7 +409,6 @@ struct mfea_handle {
   hipEvent_t run_ready[2] = {}, run_free[2] = {};
   uint8_t* run_pin[2] = {};
   size_t run_pin_bytes = 0;
-  bool opt_run_register = true;  // option "run_register": page-lock the caller's record arrays
   int run_direct = 0;            // read-only option "run_direct": the last run copied straight into them
   // generic CSR path scratch
   DevBuf<int64_t> c_indptr;
@@ -549,6 +432,16 @@ constexpr int64_t kRecMax = 9, kMMax = 6;  // record / M widths at nd = 3, block
 Part& part0(mfea_handle* h) { return *h->parts[0]; }
 bool partitioned(const mfea_handle* h) { return h->parts.size() > 1 || h->world > 1; }
 int nranks(const mfea_handle* h) { return h->world > 1 ? h->world : (int)h->parts.size(); }
+// a level's copies of the lane options
+void set_level_lanes(const Options& o, AmgLevD& d) {
+  d.rlanes = o.opt_amg_rlanes;
+  d.dsplit = o.opt_amg_down_split;
+  d.vlanes = o.opt_amg_v_lanes;
+  d.small_lanes = o.opt_amg_small_lanes;
+  d.alanes = o.opt_amg_alanes;
+  d.tail_lds = o.opt_amg_tail_lds;
+  d.ulanes = o.opt_amg_up_lanes;
+}
 
 // option keep_operator: forget what K and the hierarchies' values were formed
 // from — the next step assembles, the next GAMG solve sets up
@@ -1750,14 +1643,11 @@ int upload_amg(mfea_handle* h, Part& pt, const AmgPlan& pl, const AmgRank* rk = 
       d.t = F((size_t)nd * n);
       d.e = l ? F((size_t)nd * n) : nullptr;  // level 0 writes the CG's u
       d.coarsest = L.coarsest ? 1 : 0;
-      d.rlanes = h->opt_amg_rlanes;
-      d.dsplit = h->opt_amg_down_split;
-      d.vlanes = h->opt_amg_v_lanes;
-      d.small_lanes = h->opt_amg_small_lanes;
-      d.alanes = h->opt_amg_alanes;
-      d.tail_lds = h->opt_amg_tail_lds;
-      d.ulanes = h->opt_amg_up_lanes;
-      d.x1 = !rk && l > 0 && n <= h->opt_amg_x1_rows ? 1 : 0;
+      set_level_lanes(*h, d);
+      // levels of at most this many rows run their setup on one XCD (0: never;
+      // C3: levels 4-5 gain 1-2 µs per launch, level 3 at 8192 lost as much)
+      constexpr int64_t kAmgX1Rows = 2048;
+      d.x1 = !rk && l > 0 && n <= kAmgX1Rows ? 1 : 0;
       if (!L.coarsest) {
         d.agg = I(L.agg);
         d.P = mat(L.P, false, true);
@@ -1826,7 +1716,8 @@ int upload_amg(mfea_handle* h, Part& pt, const AmgPlan& pl, const AmgRank* rk = 
     pt.amg_cg.n = nf;
     pt.amg_cg.lo = rk && nlev ? rk->lo[0] : 0;
     pt.amg_cg.hi = rk && nlev ? rk->hi[0] : nf;
-    pt.amg_cg.w_block = h->opt_amg_w_block;
+    constexpr int kAmgWBlock = 0;  // w = A u threads per block (0: by size)
+    pt.amg_cg.w_block = kAmgWBlock;
     pt.amg_cg.w_k = amg_w_k(pl);
     pt.amg_cg.cycle = h->opt_amg_cycle;
     pt.amg_cg.coll = pt.amg_coll.kc;
@@ -5065,254 +4956,74 @@ int mfea_debug_amg_info(mfea_handle* h, int* n_levels, int64_t* rows, int64_t* b
   return 0;
 }
 
+static_assert(kOptSweepPieceMax == kSweepPieceLen && kOptBigChunkMax == mfea_handle::kRemGraphs - 1,
+              "options.hpp's bounds");
+
+// what setting an option does beyond its field (options.hpp OptEffect)
+static int option_effect(mfea_handle* h, OptEffect e) {
+  switch (e) {
+    case OptEffect::kNone:
+      break;
+    case OptEffect::kLevelLanes:
+      for (auto& pp : h->parts)
+        for (auto& L : pp->amg_lev) set_level_lanes(*h, L);
+      break;
+    case OptEffect::kCycle:
+      for (auto& pp : h->parts) {
+        pp->amg_cg.cycle = h->opt_amg_cycle;
+        for (auto& L : pp->amg_lev)
+          if (L.PT.n > 0) L.compact = h->opt_amg_cycle;
+        if (!pp->amg_lev.empty() && pp->amg_levd.n >= pp->amg_lev.size())
+          HIPC(hmemcpy(h, pp->amg_levd.ptr, pp->amg_lev.data(), pp->amg_lev.size() * sizeof(AmgLevD),
+                       hipMemcpyHostToDevice));
+      }
+      break;
+    case OptEffect::kOmega: h->amg_safe_omega = false; break;
+    case OptEffect::kReuse:  // the next solve builds for its own set
+      for (auto& pp : h->parts) pp->amg_stale = true;
+      break;
+    case OptEffect::kDistAuto: h->amg_auto.gen = -1; break;
+    case OptEffect::kGlobalPlan: h->gamg_ok = false; break;
+    case OptEffect::kDistSums:
+      for (auto& pp : h->parts) pp->amg_dist.zero_w = h->opt_dist_sums && h->world > 1 ? h->world : 0;
+      break;
+  }
+  return 0;
+}
+
+static int option_error(const OptionDesc& d) {
+  return fail(MFEA_EINVAL, std::string(d.name) + ": " + d.legal_text);
+}
+
 int mfea_set_option(mfea_handle* h, const char* name, int64_t value) {
   if (!h || !name) return fail(MFEA_EINVAL, "NULL argument");
-  const std::string n(name);
-  bool rebuild = false;  // options baked into the symbolic layout
-  if (n == "graph") h->opt_graph = value != 0;
-  else if (n == "run_register") h->opt_run_register = value != 0;
-  else if (n == "event_scratch") h->opt_event_scratch = value != 0;
-  else if (n == "phase_times") h->opt_phase_times = value != 0;
-  else if (n == "dist_graph") h->opt_dist_graph = value != 0;
-  else if (n == "order") { h->opt_order = (int)value; rebuild = true; }
-  else if (n == "lane_dof") { h->opt_lane_dof = (int)value; rebuild = true; }
-  else if (n == "cg_kernel") {
-    if (value < 0 || value > 2) return fail(MFEA_EINVAL, "cg_kernel: 0 auto, 1 lanes, 2 sell");
-    h->opt_cg_kernel = (int)value;
-  } else if (n == "ell_block") {
-    if (value != 64 && value != 128 && value != 256 && value != 512)
-      return fail(MFEA_EINVAL, "ell_block: 64, 128, 256 or 512");
-    h->opt_ell_block = (int)value;
-  } else if (n == "ell_maxg") h->opt_ell_maxg = value;
-  else if (n == "ell_compact") { h->opt_ell_compact = value != 0; rebuild = true; }
-  else if (n == "amg_tail_rows") { h->opt_amg_tail_rows = value; rebuild = true; }
-  else if (n == "amg_max_levels") {
-    if (value < 1 || value > kAmgMaxLevels) return fail(MFEA_EINVAL, "amg_max_levels: 1..32");
-    h->opt_amg_max_levels = (int)value;
-    rebuild = true;
-  }
-  else if (n == "amg_restrict_lanes") {
-    if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8 && value != 16)
-      return fail(MFEA_EINVAL, "amg_restrict_lanes: 0 (by width), 1, 2, 4, 8 or 16 (16: the compact down sweep)");
-    h->opt_amg_rlanes = (int)value;
-    for (auto& pp : h->parts)
-      for (auto& L : pp->amg_lev) L.rlanes = (int)value;
-  }
-  else if (n == "amg_v_lanes") {
-    if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8 && value != 16)
-      return fail(MFEA_EINVAL, "amg_v_lanes: 0 (by width), 1, 2, 4, 8 or 16");
-    h->opt_amg_v_lanes = (int)value;
-    for (auto& pp : h->parts)
-      for (auto& L : pp->amg_lev) L.vlanes = (int)value;
-  }
-  else if (n == "amg_small_lanes") {
-    if (value < 0 || value > (int64_t(1) << 30)) return fail(MFEA_EINVAL, "amg_small_lanes: 0 .. 2^30");
-    h->opt_amg_small_lanes = value;
-    for (auto& pp : h->parts)
-      for (auto& L : pp->amg_lev) L.small_lanes = value;
-  }
-  else if (n == "amg_merge") {
-    if (value < -1 || value > 1) return fail(MFEA_EINVAL, "amg_merge: -1 (small networks), 0 or 1");
-    h->opt_amg_merge = (int)value;
-    rebuild = true;
-  }
-  else if (n == "amg_down_split") {
-    h->opt_amg_down_split = value != 0;
-    for (auto& pp : h->parts)
-      for (auto& L : pp->amg_lev) L.dsplit = (int)(value != 0);
-  }
-  else if (n == "amg_op_lanes") {
-    if (value != 0 && value != 1 && value != 2 && value != 4)
-      return fail(MFEA_EINVAL, "amg_op_lanes: 0 (by width), 1, 2 or 4");
-    h->opt_amg_alanes = (int)value;
-    for (auto& pp : h->parts)
-      for (auto& L : pp->amg_lev) L.alanes = (int)value;
-  }
-  else if (n == "amg_tail_lds") {
-    h->opt_amg_tail_lds = value != 0;
-    for (auto& pp : h->parts)
-      for (auto& L : pp->amg_lev) L.tail_lds = (int)(value != 0);
-  }
-  else if (n == "amg_collapse" || n == "amg_collapse_mb" || n == "amg_collapse_pairs") {
-    if (n == "amg_collapse" ? (value < -1 || value >= kAmgMaxLevels)
-        : n == "amg_collapse_mb" ? (value < 0 || value > (int64_t(1) << 40 >> 20))
-                                 : (value < 0 || value >= INT32_MAX))
-      return fail(MFEA_EINVAL, n + ": out of range");
-    if (n == "amg_collapse") h->opt_amg_collapse = (int)value;
-    else if (n == "amg_collapse_mb") h->opt_amg_collapse_mb = value;
-    else h->opt_amg_collapse_pairs = value;
-    rebuild = true;
-  }
-  else if (n == "amg_spatial") {
-    if (value < -1 || value > 1) return fail(MFEA_EINVAL, "amg_spatial: -1 (by locality), 0 or 1");
-    h->opt_amg_spatial = (int)value;
-    rebuild = true;
-  }
-  else if (n == "amg_fuse_l0") {
-    if (value < -1 || value > 1) return fail(MFEA_EINVAL, "amg_fuse_l0: -1 (auto), 0 or 1");
-    h->opt_amg_fuse_l0 = (int)value;
-    rebuild = true;  // (auto also picks level 0's window)
-  }
-  else if (n == "amg_l0_window") {
-    if (value < 0 || value % 64 || value > (int64_t(1) << 30))
-      return fail(MFEA_EINVAL, "amg_l0_window: 0 (auto) or a multiple of 64 rows");
-    h->opt_amg_l0_window = value;
-    rebuild = true;
-  }
-  else if (n == "amg_up_lanes") {
-    if (value != 0 && value != 1 && value != 2 && value != 4)
-      return fail(MFEA_EINVAL, "amg_up_lanes: 0 (by width), 1, 2 or 4");
-    h->opt_amg_up_lanes = (int)value;
-    for (auto& pp : h->parts)
-      for (auto& L : pp->amg_lev) L.ulanes = (int)value;
-  }
-  else if (n == "amg_coarse_rho_ppm") {
-    if (value != 0 && (value < 100000 || value > 100000000))
-      return fail(MFEA_EINVAL, "amg_coarse_rho_ppm: 0 (Gershgorin) or 1e5 .. 1e8");
-    h->opt_amg_coarse_rho_ppm = value;
-    h->amg_safe_omega = false;
-    rebuild = true;
-  }
-  else if (n == "amg_a0_slot") {
-    if (value != 0 && value != 1) return fail(MFEA_EINVAL, "amg_a0_slot: 0 or 1");
-    h->opt_amg_a0_slot = (int)value;
-    rebuild = true;
-  }
-  else if (n == "sweep_piece") {
-    if (value < 1 || value > 64) return fail(MFEA_EINVAL, "sweep_piece: 1..64");
-    h->opt_sweep_piece = (int)value;
-    rebuild = true;
-  }
-  else if (n == "amg_fuse_setup") {
-    if (value < 0 || value > 1) return fail(MFEA_EINVAL, "amg_fuse_setup: 0 or 1");
-    h->opt_amg_fuse_setup = (int)value;
-  }
-  else if (n == "amg_theta_ppm") {
-    if (value < 0 || value > 1000000) return fail(MFEA_EINVAL, "amg_theta_ppm: 0..1000000");
-    h->opt_amg_theta_ppm = value;
-    rebuild = true;
-  }
-  else if (n == "amg_cycle") {
-    if (value != 0 && value != 1) return fail(MFEA_EINVAL, "amg_cycle: 0 (four steps per level) or 1 (compact)");
-    h->opt_amg_cycle = (int)value;
-    for (auto& pp : h->parts) {
-      pp->amg_cg.cycle = (int)value;
-      for (auto& L : pp->amg_lev)
-        if (L.PT.n > 0) L.compact = (int)value;
-      if (!pp->amg_lev.empty() && pp->amg_levd.n >= pp->amg_lev.size())
-        HIPC(hmemcpy(h, pp->amg_levd.ptr, pp->amg_lev.data(), pp->amg_lev.size() * sizeof(AmgLevD),
-                       hipMemcpyHostToDevice));
-    }
-  }
-  else if (n == "dist_timeout_ms") h->dist_timeout_s = value / 1e3;
-  else if (n == "amg_reuse") {
-    if (value < 0 || value > 1) return fail(MFEA_EINVAL, "amg_reuse: 0 (rebuild per active set) or 1");
-    h->opt_amg_reuse = (int)value;
-    for (auto& pp : h->parts) pp->amg_stale = true;  // the next solve builds for its own set
-  }
-  else if (n == "amg_rebuild_pct") {
-    if (value < 100 || value > 100000) return fail(MFEA_EINVAL, "amg_rebuild_pct: 100 .. 100000");
-    h->opt_amg_rebuild_pct = (int)value;
-  }
-  else if (n == "amg_rebuild_rent") {
-    if (value < 0 || value > 100000) return fail(MFEA_EINVAL, "amg_rebuild_rent: 0 .. 100000");
-    h->opt_amg_rebuild_rent = (int)value;
-  }
-  else if (n == "amg_dist") {
-    if (value < -1 || value > 1)
-      return fail(MFEA_EINVAL, "amg_dist: 0 (block Jacobi over partitions), 1 (global hierarchy), -1 (faster)");
-    h->opt_amg_dist = (int)value;
-    h->amg_auto.gen = -1;
-  }
-  else if (n == "amg_rep_rows") {
-    if (value < 0) return fail(MFEA_EINVAL, "amg_rep_rows: >= 0");
-    h->opt_amg_rep_rows = value;
-    h->gamg_ok = false;
-  }
-  else if (n == "amg_dist_cycle") {
-    if (value != 0 && value != 1) return fail(MFEA_EINVAL, "amg_dist_cycle: 0 (four-step) or 1 (compact)");
-    h->opt_amg_dist_cycle = (int)value;
-    h->gamg_ok = false;
-  }
-  else if (n == "dist_sums") {
-    if (value != 0 && value != 1) return fail(MFEA_EINVAL, "dist_sums: 1 (all-reduce) or 0 (send / receive pairs)");
-    h->opt_dist_sums = (int)value;
-    for (auto& pp : h->parts) pp->amg_dist.zero_w = value && h->world > 1 ? h->world : 0;
-    destroy_graph(h);  // captured chunks hold the old exchange
-  }
-  else if (n == "combo_graph") {
-    if (value != 0 && value != 1) return fail(MFEA_EINVAL, "combo_graph: 0 or 1");
-    h->opt_combo_graph = (int)value;
-  }
-  else if (n == "graph_start") {
-    if (value != 0 && value != 1) return fail(MFEA_EINVAL, "graph_start: 0 or 1");
-    h->opt_graph_start = (int)value;
-  }
-  else if (n == "step_graph") {
-    if (value != 0 && value != 1) return fail(MFEA_EINVAL, "step_graph: 0 or 1");
-    h->opt_step_graph = (int)value;
-  }
-  else if (n == "batch_graph") {
-    if (value != 0 && value != 1) return fail(MFEA_EINVAL, "batch_graph: 0 or 1");
-    h->opt_batch_graph = (int)value;
-  }
-  else if (n == "setup_entry") {
-    if (value != 0 && value != 1) return fail(MFEA_EINVAL, "setup_entry: 0 or 1");
-    h->opt_setup_entry = (int)value;
-  }
-  else if (n == "spec_post") {
-    if (value != 0 && value != 1) return fail(MFEA_EINVAL, "spec_post: 0 or 1");
-    h->opt_spec_post = (int)value;
-  }
-  else if (n == "asm_kernel") {
-    if (value < 0 || value > 2)
-      return fail(MFEA_EINVAL, "asm_kernel: 0 (row gather), 1 (element colours), 2 (element pass + row pass)");
-    h->opt_asm_kernel = (int)value;
-  }
-  else if (n == "cc_tile") {
-    if (value != 512 && value != 1024 && value != 2048 && value != 4096)
-      return fail(MFEA_EINVAL, "cc_tile: 512, 1024, 2048 or 4096");
-    h->opt_cc_tile = (int)value;
-  }
-  else if (n == "part_slack_pct") {
-    if (value < 0 || value > 45) return fail(MFEA_EINVAL, "part_slack_pct: 0..45");
-    h->opt_part_slack = value / 100.0;
-    rebuild = true;
-  }
-  else if (n == "keep_operator") {
-    if (value != 0 && value != 1) return fail(MFEA_EINVAL, "keep_operator: 0 or 1");
-    h->opt_keep_operator = (int)value;
-  }
-  else if (n == "amg_close") {
-    if (value != 0 && value != 1) return fail(MFEA_EINVAL, "amg_close: 0 or 1");
-    h->opt_amg_close = (int)value;
-  }
-  else if (n == "amg_start") {
-    if (value != 0 && value != 1) return fail(MFEA_EINVAL, "amg_start: 0 or 1");
-    h->opt_amg_start = (int)value;
-  }
-  else if (n == "amg_lazy_px") {
-    if (value != 0 && value != 1) return fail(MFEA_EINVAL, "amg_lazy_px: 0 or 1");
-    h->opt_amg_lazy_px = (int)value;
-  }
-  else if (n == "amg_big_chunk") {
-    if (value < 2 || value >= mfea_handle::kRemGraphs) return fail(MFEA_EINVAL, "amg_big_chunk: 2..63");
-    h->opt_amg_big_chunk = (int)value;
-  }
-  else return fail(MFEA_EINVAL, "unknown option " + n);
+  const OptionDesc* d = find_option(name);
+  if (!d) return fail(MFEA_EINVAL, std::string("unknown option ") + name);
+  if (!option_legal(*d, value)) return option_error(*d);
+  option_store(*d, *h, value);
+  RC(option_effect(h, d->effect));
   // kept K / hierarchy values: dropped by every option but the few that
   // cannot change a value (conservative: most options only change launches)
-  if (n != "phase_times" && n != "run_register" && !(n == "keep_operator" && value == 1) &&
-      n != "amg_close" && n != "amg_start" && n != "amg_lazy_px" && n != "amg_big_chunk")
-    drop_kept(h);
-  destroy_graph(h);  // captured graphs hold the old geometry
-  if (rebuild) {
+  if (!option_keeps(*d, value)) drop_kept(h);
+  destroy_graph(h);  // captured graphs hold the old geometry (dist_sums: the old exchange)
+  if (d->rebuilds_layout) {
     if (!h->dirty && h->Ecount) {  // keep the current activity across the rebuild
       RC(set_device(h));
       RC(gather_active(h, h->active_host));
     }
     h->dirty = true;
   }
+  return 0;
+}
+
+int mfea_debug_option_check(const char* name, int64_t value, int64_t* stored) {
+  if (!name || !stored) return fail(MFEA_EINVAL, "NULL argument");
+  const OptionDesc* d = find_option(name);
+  if (!d) return fail(MFEA_EINVAL, std::string("unknown option ") + name);
+  if (!option_legal(*d, value)) return option_error(*d);
+  Options scratch;
+  option_store(*d, scratch, value);
+  *stored = d->load(scratch);
   return 0;
 }
 
@@ -5431,117 +5142,92 @@ int mfea_debug_amg_vector(mfea_handle* h, int l, int which, double* out, int64_t
   return 0;
 }
 
+// The read-only names of mfea_get_option: name, value, and whether it is read
+// from partition 0's plan (MFEA_ESTATE before there is one; p is null there).
+namespace {
+int64_t stored_blocks(const std::vector<int32_t>& col) {
+  int64_t nb = 0;
+  for (int32_t c : col) nb += c >= 0;
+  return nb;
+}
+int64_t asm_colours(const mfea_handle* h) {
+  int64_t nc = 0;
+  for (auto& pp : h->parts) nc = std::max<int64_t>(nc, pp->ec_state > 0 ? pp->ec.colors : 0);
+  return nc;
+}
+struct ReadOnly {
+  const char* name;
+  bool part;
+  int64_t (*get)(const mfea_handle* h, const Part* p);
+};
+#define RO(name, part, expr) \
+  {name, part, [](const mfea_handle* h, const Part* p) -> int64_t { return (void)h, (void)p, expr; }}
+const ReadOnly kReadOnly[] = {
+    RO("element_props", false, h->has_props()),  // per-element columns are set
+    RO("run_direct", false, h->run_direct),      // the last mfea_run's host path
+    RO("amg_merged", true, p->amg_mg.on),        // the plan's cycle form
+    RO("amg_merge_dq_blocks", true, p->amg_mplan.on ? stored_blocks(p->amg_mplan.DQ.col) : 0),
+    RO("amg_merge_u_blocks", true, p->amg_mplan.on ? stored_blocks(p->amg_mplan.U.col) : 0),
+    RO("sweep_colors", true, p->sweep.colors),
+    RO("sweep_pieces", true, p->sweep.n_pieces),
+    // partition 0's plan: the fused launch is in use; level 0's window; the
+    // largest block halo and the capacity it was held against
+    RO("amg_fused_l0", false, p && amg_fused(h, *p)),
+    RO("amg_l0_window_used", false, p ? p->amg.l0_window : 0),
+    RO("amg_fuse_max_halo", false, p ? p->amg_fplan.max_halo : 0),
+    RO("amg_fuse_halo_cap", false, p ? amg_fuse_halo_cap(p->amg.nd, p->amg.l0_window) : 0),
+    RO("amg_safe_omega", false, h->amg_safe_omega),
+    // partition 0's collapsed level kc (0: none), the stored blocks of its V
+    RO("amg_collapse_level", false, p ? p->amg_coll.kc : 0),
+    RO("amg_collapse_blocks", false, p && p->amg_coll.kc > 0 ? stored_blocks(p->amg_coll.lev[0].V.col) : 0),
+    RO("amg_spatial_chosen", false, p && p->amg.spatial),  // the plan is in Z-order
+    RO("amg_reused", true, p->amg_reused),  // the last solve kept a hierarchy built for another set
+    RO("amg_build_iters", true, p->amg_build_iters),
+    // the partitioned form in use (-1: the automatic choice still undecided)
+    RO("amg_dist_chosen", false, h->opt_amg_dist >= 0 ? h->opt_amg_dist : h->amg_auto.choice),
+    RO("op_kept_steps", false, h->op_kept_steps),      // steps that skipped the assembly
+    RO("amg_setup_kept", false, h->amg_setup_kept),    // solves that skipped the numeric setup
+    RO("amg_px_replays", false, h->amg_px_replays),    // p, x replay launches the solves queued
+    RO("amg_px_slots", false, kAmgPxSlots),            // u slots of the lazy p, x chain
+    RO("amg_start_fused", false, h->amg_start_fused),  // solves that started with k_amg_start
+    RO("amg_close_hits", false, h->amg_close_hits),    // solves ended by the closing check
+    RO("amg_last_cycles", false, h->amg_last_cycles),  // V-cycles the last solve queued
+    RO("asm_colours", false, asm_colours(h)),
+};
+#undef RO
+}  // namespace
+
 int mfea_get_option(mfea_handle* h, const char* name, int64_t* value) {
   if (!h || !name || !value) return fail(MFEA_EINVAL, "NULL argument");
-  const std::string n(name);
-  // the read-only plan values need a partition to read them from
-  static const char* plan_names[] = {"amg_merged", "amg_merge_dq_blocks", "amg_merge_u_blocks", "sweep_colors",
-                                     "sweep_pieces", "amg_reused", "amg_build_iters"};
-  for (const char* pn : plan_names)
-    if (n == pn && h->parts.empty()) return fail(MFEA_ESTATE, std::string(name) + ": no partition yet");
-  if (n == "graph") *value = h->opt_graph;
-  else if (n == "run_register") *value = h->opt_run_register ? 1 : 0;
-  else if (n == "event_scratch") *value = h->opt_event_scratch;
-  else if (n == "element_props") *value = h->has_props() ? 1 : 0;  // read-only: per-element columns are set
-  else if (n == "run_direct") *value = h->run_direct;  // read-only: the last mfea_run's host path
-  else if (n == "phase_times") *value = h->opt_phase_times ? 1 : 0;
-  else if (n == "dist_graph") *value = h->opt_dist_graph;
-  else if (n == "order") *value = h->opt_order;
-  else if (n == "lane_dof") *value = h->opt_lane_dof;
-  else if (n == "cg_kernel") *value = h->opt_cg_kernel;
-  else if (n == "ell_block") *value = h->opt_ell_block;
-  else if (n == "ell_maxg") *value = h->opt_ell_maxg;
-  else if (n == "ell_compact") *value = h->opt_ell_compact;
-  else if (n == "amg_tail_rows") *value = h->opt_amg_tail_rows;
-  else if (n == "amg_max_levels") *value = h->opt_amg_max_levels;
-  else if (n == "amg_restrict_lanes") *value = h->opt_amg_rlanes;
-  else if (n == "amg_down_split") *value = h->opt_amg_down_split;
-  else if (n == "amg_v_lanes") *value = h->opt_amg_v_lanes;
-  else if (n == "amg_merge") *value = h->opt_amg_merge;
-  else if (n == "amg_merged") *value = part0(h).amg_mg.on;  // read-only: the plan's cycle form
-  else if (n == "amg_merge_dq_blocks" || n == "amg_merge_u_blocks") {  // read-only: stored blocks of DQ / U
-    const AmgMerge& M = part0(h).amg_mplan;
-    int64_t nb = 0;
-    if (M.on)
-      for (int32_t c : (n == "amg_merge_dq_blocks" ? M.DQ.col : M.U.col)) nb += c >= 0;
-    *value = nb;
+  if (const OptionDesc* d = find_option(name)) {
+    *value = d->load(*h);
+    return 0;
   }
-  else if (n == "amg_small_lanes") *value = h->opt_amg_small_lanes;
-  else if (n == "amg_op_lanes") *value = h->opt_amg_alanes;
-  else if (n == "amg_tail_lds") *value = h->opt_amg_tail_lds;
-  else if (n == "amg_cycle") *value = h->opt_amg_cycle;
-  else if (n == "amg_theta_ppm") *value = h->opt_amg_theta_ppm;
-  else if (n == "amg_fuse_setup") *value = h->opt_amg_fuse_setup;
-  else if (n == "sweep_piece") *value = h->opt_sweep_piece;
-  else if (n == "sweep_colors") *value = part0(h).sweep.colors;  // read-only
-  else if (n == "sweep_pieces") *value = part0(h).sweep.n_pieces;  // read-only
-  else if (n == "amg_up_lanes") *value = h->opt_amg_up_lanes;
-  else if (n == "amg_fuse_l0") *value = h->opt_amg_fuse_l0;
-  else if (n == "amg_l0_window") *value = h->opt_amg_l0_window;
-  // read-only, partition 0's plan: the fused launch is in use; level 0's
-  // window; the largest block halo and the capacity it was held against
-  else if (n == "amg_fused_l0") *value = !h->parts.empty() && amg_fused(h, *h->parts[0]) ? 1 : 0;
-  else if (n == "amg_l0_window_used") *value = h->parts.empty() ? 0 : h->parts[0]->amg.l0_window;
-  else if (n == "amg_fuse_max_halo") *value = h->parts.empty() ? 0 : h->parts[0]->amg_fplan.max_halo;
-  else if (n == "amg_fuse_halo_cap")
-    *value = h->parts.empty() ? 0 : amg_fuse_halo_cap(h->parts[0]->amg.nd, h->parts[0]->amg.l0_window);
-  else if (n == "amg_coarse_rho_ppm") *value = h->opt_amg_coarse_rho_ppm;
-  else if (n == "amg_a0_slot") *value = h->opt_amg_a0_slot;
-  else if (n == "amg_safe_omega") *value = h->amg_safe_omega ? 1 : 0;  // read-only
-  else if (n == "amg_spatial") *value = h->opt_amg_spatial;
-  else if (n == "amg_collapse") *value = h->opt_amg_collapse;
-  else if (n == "amg_collapse_mb") *value = h->opt_amg_collapse_mb;
-  else if (n == "amg_collapse_pairs") *value = h->opt_amg_collapse_pairs;
-  else if (n == "amg_collapse_level") {  // read-only: partition 0's collapsed level kc (0: none)
-    *value = h->parts.empty() ? 0 : h->parts[0]->amg_coll.kc;
+  for (const ReadOnly& r : kReadOnly)
+    if (std::strcmp(r.name, name) == 0) {
+      const Part* p = h->parts.empty() ? nullptr : h->parts[0].get();
+      if (r.part && !p) return fail(MFEA_ESTATE, std::string(name) + ": no partition yet");
+      *value = r.get(h, p);
+      return 0;
+    }
+  return fail(MFEA_EINVAL, std::string("unknown option ") + name);
+}
+
+int mfea_debug_option_info(int index, const char** name, int64_t* dflt, int* flags) {
+  if (!name || !dflt || !flags) return fail(MFEA_EINVAL, "NULL argument");
+  const int nw = option_count(), nr = (int)(sizeof kReadOnly / sizeof kReadOnly[0]);
+  if (index < 0 || index >= nw + nr) return fail(MFEA_EINVAL, "option index out of range");
+  if (index < nw) {
+    const OptionDesc& d = option_at(index);
+    *name = d.name;
+    *dflt = option_default(d);
+    *flags = MFEA_OPT_WRITABLE | (d.rebuilds_layout ? MFEA_OPT_REBUILDS_LAYOUT : 0) |
+             (d.keeps_kept == OptKeeps::kYes ? MFEA_OPT_KEEPS_KEPT : 0);
+  } else {
+    *name = kReadOnly[index - nw].name;
+    *dflt = 0;
+    *flags = 0;
   }
-  else if (n == "amg_collapse_blocks") {  // read-only: stored blocks of the collapsed V at kc
-    int64_t nb = 0;
-    if (!h->parts.empty() && h->parts[0]->amg_coll.kc > 0)
-      for (int32_t c : h->parts[0]->amg_coll.lev[0].V.col) nb += c >= 0;
-    *value = nb;
-  }
-  else if (n == "amg_spatial_chosen") {  // read-only: partition 0's plan is in Z-order
-    *value = h->parts.empty() ? 0 : (h->parts[0]->amg.spatial ? 1 : 0);
-  }
-  else if (n == "dist_timeout_ms") *value = (int64_t)std::llround(h->dist_timeout_s * 1e3);
-  else if (n == "amg_dist") *value = h->opt_amg_dist;
-  else if (n == "amg_reuse") *value = h->opt_amg_reuse;
-  else if (n == "amg_rebuild_pct") *value = h->opt_amg_rebuild_pct;
-  else if (n == "amg_rebuild_rent") *value = h->opt_amg_rebuild_rent;
-  else if (n == "amg_reused") *value = part0(h).amg_reused ? 1 : 0;  // read-only: the last solve kept a hierarchy built for another set
-  else if (n == "amg_build_iters") *value = part0(h).amg_build_iters;  // read-only
-  else if (n == "amg_dist_chosen")  // read-only: the form in use (-1: the automatic choice still undecided)
-    *value = h->opt_amg_dist >= 0 ? h->opt_amg_dist : h->amg_auto.choice;
-  else if (n == "amg_rep_rows") *value = h->opt_amg_rep_rows;
-  else if (n == "cc_tile") *value = h->opt_cc_tile;
-  else if (n == "asm_kernel") *value = h->opt_asm_kernel;
-  else if (n == "spec_post") *value = h->opt_spec_post;
-  else if (n == "setup_entry") *value = h->opt_setup_entry;
-  else if (n == "batch_graph") *value = h->opt_batch_graph;
-  else if (n == "step_graph") *value = h->opt_step_graph;
-  else if (n == "graph_start") *value = h->opt_graph_start;
-  else if (n == "combo_graph") *value = h->opt_combo_graph;
-  else if (n == "keep_operator") *value = h->opt_keep_operator;
-  else if (n == "op_kept_steps") *value = h->op_kept_steps;    // read-only: steps that skipped the assembly
-  else if (n == "amg_setup_kept") *value = h->amg_setup_kept;  // read-only: solves that skipped the numeric setup
-  else if (n == "amg_close") *value = h->opt_amg_close;
-  else if (n == "amg_start") *value = h->opt_amg_start;
-  else if (n == "amg_lazy_px") *value = h->opt_amg_lazy_px;
-  else if (n == "amg_big_chunk") *value = h->opt_amg_big_chunk;
-  else if (n == "amg_px_replays") *value = h->amg_px_replays;  // read-only: p, x replay launches the solves queued
-  else if (n == "amg_px_slots") *value = kAmgPxSlots;          // read-only: u slots of the lazy p, x chain
-  else if (n == "amg_start_fused") *value = h->amg_start_fused;  // read-only: solves that started with k_amg_start
-  else if (n == "amg_close_hits") *value = h->amg_close_hits;    // read-only: solves ended by the closing check
-  else if (n == "amg_last_cycles") *value = h->amg_last_cycles;  // read-only: V-cycle applications the last solve queued
-  else if (n == "asm_colours") {
-    *value = 0;
-    for (auto& pp : h->parts) *value = std::max<int64_t>(*value, pp->ec_state > 0 ? pp->ec.colors : 0);
-  }
-  else if (n == "amg_dist_cycle") *value = h->opt_amg_dist_cycle;
-  else if (n == "dist_sums") *value = h->opt_dist_sums;
-  else if (n == "part_slack_pct") *value = (int64_t)std::llround(h->opt_part_slack * 100.0);
-  else return fail(MFEA_EINVAL, "unknown option " + n);
   return 0;
 }
 

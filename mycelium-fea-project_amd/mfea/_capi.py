@@ -12,19 +12,6 @@ import os
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# mfea_set_option defaults (include/mfea_debug.h)
-DEFAULT_OPTIONS = {"graph": 1, "phase_times": 0, "dist_graph": 1, "order": -1, "lane_dof": 0, "cg_kernel": 0,
-                   "ell_block": 256, "ell_maxg": 0, "ell_compact": 1, "amg_tail_rows": 2048,
-                   "amg_max_levels": 32, "amg_restrict_lanes": 0, "amg_op_lanes": 0,
-                   "amg_tail_lds": 1, "dist_timeout_ms": 60000, "part_slack_pct": 35, "amg_dist": -1,
-                   "amg_rep_rows": 32768, "amg_dist_cycle": 1, "dist_sums": 1, "amg_cycle": 1, "amg_fuse_setup": 1,
-                   "amg_up_lanes": 0, "amg_spatial": -1, "amg_collapse": -1, "amg_collapse_mb": 32,
-                   "amg_collapse_pairs": 8000000, "amg_theta_ppm": 0, "amg_reuse": 1, "amg_rebuild_pct": 800, "amg_rebuild_rent": 100,
-                   "amg_coarse_rho_ppm": 1750000, "sweep_piece": 64, "cc_tile": 1024,
-                   "asm_kernel": 0, "spec_post": 1, "setup_entry": 1,
-                   "batch_graph": 1, "step_graph": 0,
-                   "graph_start": 1, "combo_graph": 1, "amg_a0_slot": 1, "run_register": 1,
-                   "keep_operator": 1, "event_scratch": 1}
 CG_KERNEL = {"auto": 0, "lanes": 1, "sell": 2}
 
 LIB_PATH = os.environ.get("MFEA_LIB", os.path.join(os.path.dirname(_HERE), "libmfea.so"))
@@ -175,6 +162,9 @@ _sig = {
     "mfea_debug_floating": (C.c_int, [_P, C.c_void_p]),
     "mfea_set_option": (C.c_int, [_P, C.c_char_p, C.c_int64]),
     "mfea_get_option": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int64)]),
+    "mfea_debug_option_info": (C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64),
+                                         C.POINTER(C.c_int)]),
+    "mfea_debug_option_check": (C.c_int, [C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]),
     "mfea_debug_amg_vcycle": (C.c_int, [_P, _P, _P]),
     "mfea_debug_amg_vector": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "mfea_debug_amg_info": (C.c_int, [_P, C.POINTER(C.c_int), _P, _P, _P, C.c_int,
@@ -225,6 +215,33 @@ def _ptr(a):
 
 def abi_version() -> int:
     return _lib.mfea_abi_version()
+
+
+OPT_WRITABLE, OPT_REBUILDS_LAYOUT, OPT_KEEPS_KEPT = 1, 2, 4
+
+
+def option_info():
+    """Every option the library knows, without a handle (mfea_debug_option_info):
+    (name, default, flags) of the writable ones in the library's table order,
+    then of the read-only names (default 0, flags 0)."""
+    out = []
+    name, dflt, flags = C.c_char_p(), C.c_int64(), C.c_int()
+    while _lib.mfea_debug_option_info(len(out), C.byref(name), C.byref(dflt), C.byref(flags)) == OK:
+        out.append((name.value.decode(), dflt.value, flags.value))
+    return out
+
+
+def option_check(name: str, value: int) -> int:
+    """What get_option would read back after set_option(name, value), without a
+    handle (mfea_debug_option_check); MfeaError(EINVAL) where set_option would
+    refuse."""
+    v = C.c_int64()
+    _check(_lib.mfea_debug_option_check(name.encode(), int(value), C.byref(v)))
+    return v.value
+
+
+# mfea_set_option's defaults, from the library's own table
+DEFAULT_OPTIONS = {n: d for n, d, f in option_info() if f & OPT_WRITABLE}
 
 
 def dist_unique_id() -> bytes:

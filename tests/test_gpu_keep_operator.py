@@ -259,3 +259,31 @@ def test_rtol_change_keeps():
     assert out[1][2]["iters"] > out[1][1]["iters"]  # (the tolerance did change the solve)
     for k, (a, b) in enumerate(zip(out[1], out[0])):
         _same(a, b, k)
+
+
+def _writable_options():
+    from mfea import _capi
+    return [(n, bool(f & _capi.OPT_KEEPS_KEPT)) for n, _, f in _capi.option_info() if f & _capi.OPT_WRITABLE]
+
+
+@pytest.mark.parametrize("name,keeps", _writable_options())
+def test_setting_an_option_keeps_or_drops_the_kept_operator(name, keeps):
+    """Setting an option — here to the value it has, so nothing else changes —
+    drops the kept K and hierarchy values unless the option's table row says
+    it keeps them (mfea_debug_option_info's MFEA_OPT_KEEPS_KEPT; keep_operator
+    itself keeps when set to 1).  Either way the next step's results are those
+    of the kept step before it at the same grip displacement, bit for bit."""
+    keeps = keeps or name == "keep_operator"
+    eng = _engine("3d", 1)
+    try:
+        _record(eng, DYS[0], _gamg())
+        kept = _record(eng, DYS[1], _gamg())
+        c1 = _counters(eng)
+        assert c1 == (1, 1)  # (the second step was a kept one)
+        eng.set_option(name, 1 if name == "keep_operator" else eng.get_option(name))
+        after = _record(eng, DYS[1], _gamg())
+        c2 = _counters(eng)
+    finally:
+        eng.close()
+    assert c2 == ((2, 2) if keeps else (1, 1)), (name, c2)
+    assert after["force"] == kept["force"] and np.array_equal(after["U"], kept["U"])
