@@ -158,6 +158,58 @@ int mfea_set_element_props(mfea_handle* h, const mfea_element_props* p);
  * NaN, because that scalar belongs to the call, not to the handle. */
 int mfea_get_element_props(mfea_handle* h, double* E, double* A, double* I, double* max_strain);
 
+/* ---- grip motion: shear, mixed-mode and out-of-plane tests ------------------ */
+/* Direction of the grip motion.  Prescribed displacement of a top-band node =
+ * dy_top·top[c], of a bottom-band node = dy_bot·bot[c], c = x, y, z: one f64
+ * multiplication per component; dy_top / dy_bot are the amplitudes every
+ * solve / step / run / event call already takes.  Default (0,1,0), (0,1,0):
+ * the tensile test.  NULL for either = leave it as it is.  Not normalised.
+ *   RHS       a free row with a known neighbour of class top or bottom takes
+ *             b −= V·p with V the neighbour's whole symmetric 3×3 block and
+ *             p[c] = fl(amplitude·direction[c]); each row of V·p is one fma
+ *             chain in component order (x, y, z), the neighbours in slot order.
+ *             A known row gets x = p.  A node in both bands takes the bottom
+ *             value, as in the tensile test.
+ *   force     wherever the API returns a force (total_force of mfea_post /
+ *             mfea_step, mfea_run_records.force, force1 of events) it is the
+ *             work-conjugate one,
+ *               F = (top[0]·S[0] + top[1]·S[1]) + top[2]·S[2],
+ *               S[c] = Σ_{top rows} (K·U)[3n+c]  (mfea_get_reaction's top),
+ *             f64 products and sums in exactly this order, no fused operation.
+ *             For (0,1,0) that is the tensile test's F_y.
+ *   events    U ∝ amplitude on a fixed active set whatever the direction:
+ *             mfea_event's rules stand unchanged, force1 as above.
+ * MFEA_EINVAL, the handle unchanged, unless every component given is finite
+ * and no vector given is all zero.  The directions are handle state, as the
+ * material is: mfea_set_mesh, mfea_set_bc, mfea_set_active, mfea_set_material
+ * and mfea_set_element_props keep them.
+ * One partition only: MFEA_ESTATE on a partitioned handle; a handle with
+ * another direction than the default that is partitioned afterwards returns
+ * MFEA_ESTATE from its next build.
+ * Default state: at (0,1,0), (0,1,0) — never set, or set explicitly — the
+ * handle takes the kernels, launches and graphs of the tensile engine, and
+ * every result is bit for bit that engine's, for every preconditioner.
+ * A change keeps K, the symbolic hierarchy and everything option
+ * "keep_operator" keeps (none depends on the direction: the next step is a
+ * kept step, amg_rebuilt == 0); it drops the right-hand side a step cached
+ * and every captured graph, which hold the old vectors by value.
+ * Planar meshes (every z == 0): with every z component zero the 2-DOF lane
+ * path runs as in the tensile test (x and y are both in the plane).  With a
+ * non-zero z component in either vector the handle solves with 3 DOFs per
+ * node, as option "lane_dof" 3 makes it, and the change takes the rebuild a
+ * layout option takes (the activity is kept).  The axial strain of an
+ * out-of-plane motion on a planar mesh is zero to first order: no element
+ * fails, and an event there is the unloaded terminal event (lam = +inf,
+ * MFEA_EVENTS_UNLOADED). */
+int mfea_set_grip_motion(mfea_handle* h, const double top[3], const double bot[3]);
+int mfea_get_grip_motion(mfea_handle* h, double top[3], double bot[3]);
+/* Σ over the band's rows of (K·U)[3n+c], c = x, y, z, on the unregularised K
+ * of the last assembly and the current U (MFEA_ESTATE: no assembly since the
+ * last build; one partition only).  Either may be NULL.  A node in both bands
+ * counts in the bottom one.  The y sum of the top band has total_force's bits
+ * in the tensile test. */
+int mfea_get_reaction(mfea_handle* h, double top[3], double bot[3]);
+
 /* ---- mesh + boundary conditions (symbolic, once per mesh) ------------------ */
 /* Replaces the CSV→array hand-off of fea_solver (src/fea_solver.py:193-201) and
  * read_nodes_csv/read_elems_csv (src/fea_petsc.cpp:42-82, 179-200).

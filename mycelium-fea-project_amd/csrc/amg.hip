@@ -1406,18 +1406,22 @@ __global__ __launch_bounds__(kBlock) void k_amg_row0_inverse(AmgCg cg, int32_t* 
 // vcycle_entry: level 0's D⁻¹ and ω must be current, i.e. the setup kept),
 // and the reduction's last block k_cg_init_finalize's: the state, and the
 // zeroing of the partial buffers.
-template <int ND>
+// GM: GripY, or GripVec — k_amg_rhs<GripVec>'s row body (kernels.hpp).
+template <int ND, class GM>
 __global__ __launch_bounds__(kBlock) void k_amg_start(SellOp op, const uint8_t* __restrict__ code, double dy_top,
                                                       double dy_bot, CgVecs v, double* partials, unsigned* ticket,
                                                       double* red_out, AmgLevD L0, AmgCg cg,
                                                       const int32_t* __restrict__ inv, double rtol, double atol,
                                                       int norm, int max_it, double reg, SolveState* st,
-                                                      double* zero, int64_t nzero) {
+                                                      double* zero, int64_t nzero, GM g) {
   const int64_t row = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   double acc[2] = {0.0, 0.0};
+  constexpr bool VEC = std::is_same<GM, GripVec>::value;
+  GripP gp{};
+  if constexpr (VEC) gp = grip_disp(g, dy_top, dy_bot);
   if (row < op.nf) {
     double b[3];
-    amg_rhs_row(op, code, dy_top, dy_bot, row, b);
+    amg_rhs_row<GM>(op, code, dy_top, dy_bot, row, b, &gp);
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       v.r[0][3 * row + a] = b[a];
@@ -1439,9 +1443,16 @@ __global__ __launch_bounds__(kBlock) void k_amg_start(SellOp op, const uint8_t* 
     }
   } else if (row < op.N) {
     const uint8_t c = code[row];
-    v.x[3 * row] = 0.0;
-    v.x[3 * row + 1] = c == 3 ? 0.0 : (c == 2 ? dy_bot : dy_top);
-    v.x[3 * row + 2] = 0.0;
+    if constexpr (VEC) {
+      double xk[3];
+      grip_of(gp, c, xk);
+#pragma unroll
+      for (int a = 0; a < 3; ++a) v.x[3 * row + a] = xk[a];
+    } else {
+      v.x[3 * row] = 0.0;
+      v.x[3 * row + 1] = c == 3 ? 0.0 : (c == 2 ? dy_bot : dy_top);
+      v.x[3 * row + 2] = 0.0;
+    }
   }
   if (!block_publish<2>(acc, partials, ticket, red_out)) return;
   for (int64_t k = threadIdx.x; k < nzero; k += kBlock) zero[k] = 0.0;
@@ -2313,14 +2324,20 @@ void launch_amg_row0_inverse(hipStream_t s, const AmgCg& cg, int32_t* inv, int64
 void launch_amg_start(hipStream_t s, int nd, const SellOp& op, const uint8_t* code, double dy_top, double dy_bot,
                       const CgVecs& v, double* partials, unsigned* ticket, double* red_out, const AmgLevD& L0,
                       const AmgCg& cg, const int32_t* inv, double rtol, double atol, int norm, int max_it,
-                      double reg, SolveState* st, double* zero, int64_t nzero) {
+                      double reg, SolveState* st, double* zero, int64_t nzero, const GripVec* grip) {
   const dim3 grid((unsigned)grid_rows(op.N > 0 ? op.N : 1));  // k_amg_rhs's (launch_cg_rhs)
-  if (nd == 2)
-    hipLaunchKernelGGL(k_amg_start<2>, grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials, ticket,
-                       red_out, L0, cg, inv, rtol, atol, norm, max_it, reg, st, zero, nzero);
+  if (grip && nd == 2)
+    hipLaunchKernelGGL((k_amg_start<2, GripVec>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials,
+                       ticket, red_out, L0, cg, inv, rtol, atol, norm, max_it, reg, st, zero, nzero, *grip);
+  else if (grip)
+    hipLaunchKernelGGL((k_amg_start<3, GripVec>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials,
+                       ticket, red_out, L0, cg, inv, rtol, atol, norm, max_it, reg, st, zero, nzero, *grip);
+  else if (nd == 2)
+    hipLaunchKernelGGL((k_amg_start<2, GripY>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials,
+                       ticket, red_out, L0, cg, inv, rtol, atol, norm, max_it, reg, st, zero, nzero, GripY{});
   else
-    hipLaunchKernelGGL(k_amg_start<3>, grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials, ticket,
-                       red_out, L0, cg, inv, rtol, atol, norm, max_it, reg, st, zero, nzero);
+    hipLaunchKernelGGL((k_amg_start<3, GripY>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials,
+                       ticket, red_out, L0, cg, inv, rtol, atol, norm, max_it, reg, st, zero, nzero, GripY{});
 }
 
 template <int ND, int BS>

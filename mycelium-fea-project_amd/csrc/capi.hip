@@ -277,6 +277,17 @@ struct mfea_handle : Options {
   const double2* sec_d() const { return pe_sec.empty() ? nullptr : reinterpret_cast<const double2*>(pe_sec_d.ptr); }
   const double* Ee_d() const { return pe_E.empty() ? nullptr : pe_E_d.ptr; }
   const double* strength_d() const { return pe_S.empty() ? nullptr : pe_S_d.ptr; }
+  // mfea_set_grip_motion (one partition): the directions of the grip motion,
+  // handle state as the material is.  The tensile test's pair takes the
+  // kernels as they were (grip_arg NULL: the GripY instantiations); any other
+  // the GripVec ones.  Nothing of K or the hierarchies depends on them.
+  GripVec grip{{0.0, 1.0, 0.0}, {0.0, 1.0, 0.0}};
+  bool grip_default() const {
+    return grip.top[0] == 0.0 && grip.top[1] == 1.0 && grip.top[2] == 0.0 && grip.bot[0] == 0.0 &&
+           grip.bot[1] == 1.0 && grip.bot[2] == 0.0;
+  }
+  const GripVec* grip_arg() const { return grip_default() ? nullptr : &grip; }
+  bool grip_z() const { return grip.top[2] != 0.0 || grip.bot[2] != 0.0; }
   // host-side mesh/BC (original order)
   int64_t N = 0, Ecount = 0;
   std::vector<double> xyz;
@@ -568,9 +579,10 @@ int set_device(mfea_handle* h) {
 // 0 natural, > 1 degree sort inside windows of that many rows).
 int order_mode(const mfea_handle* h) { return h->opt_order; }
 
-// planar meshes run with 2 DOFs per node (option "lane_dof" 3 forces 3);
+// planar meshes run with 2 DOFs per node (option "lane_dof" 3 forces 3, and
+// so does a grip motion with a z component: the solution leaves the plane);
 // decided on the whole mesh so every partition exchanges records of one width
-int lane_dofs(const mfea_handle* h) { return (h->planar && h->opt_lane_dof != 3) ? 2 : 3; }
+int lane_dofs(const mfea_handle* h) { return (h->planar && h->opt_lane_dof != 3 && !h->grip_z()) ? 2 : 3; }
 
 // Waits for an event.  Partitioned over RCCL: polls with a deadline and the
 // communicator's error state, so a lost peer ends the call instead of hanging.
@@ -637,7 +649,7 @@ int upload_part(mfea_handle* h, Part& pt, bool dm) {
   HIPC(pt.cg_part.alloc(3 * 4 * kCgMaxPartials));
   HIPC(pt.dinv.alloc(6 * N));
   HIPC(pt.stress.alloc(E));
-  HIPC(pt.partials.alloc(4 * (maxg + 16)));
+  HIPC(pt.partials.alloc(5 * (maxg + 16)));  // (the widest user: the event scan with three reaction sums)
   HIPC(pt.red.alloc(16));
   HIPC(pt.slice_ptr.alloc(P.slice_ptr.size()));
   HIPC(pt.row_len.alloc(N));
@@ -768,6 +780,8 @@ int ensure_built(mfea_handle* h) {
   const bool dm = h->world > 1 || h->nparts > 1;
   if (dm && h->has_props())
     return fail(MFEA_ESTATE, "per-element properties: one partition per handle (mfea_set_element_props(h, NULL) first)");
+  if (dm && !h->grip_default())
+    return fail(MFEA_ESTATE, "grip motion: one partition per handle (set the directions (0,1,0), (0,1,0) first)");
   const int np = h->world > 1 ? 1 : h->nparts;
   const bool skip = (h->mesh_flags & MFEA_MESH_SKIP_INVALID) != 0;
   h->parts.clear();
@@ -1300,7 +1314,7 @@ int solve_impl(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_op
   const CgVecs v = cg_vecs(pt);
   RC(phase_event(h, h->ev[1], s));
   launch_cg_rhs(s, op, pt.code.ptr, dy_top, dy_bot, o->reg, precond, v, pt.partials.ptr, tix(pt, 0),
-                pt.red.ptr);
+                pt.red.ptr, h->grip_arg());
   launch_cg_init_finalize(s, pt.red.ptr, o->rtol, o->atol, o->norm, o->max_it, o->reg,
                           pt.state.ptr,
                           pt.cg_part.ptr, 2 * 4 * kCgMaxPartials);
@@ -2325,6 +2339,8 @@ void enqueue_step_head(mfea_handle* h, Part& pt, const mfea_solve_opts* o) {
   q.top_end = P.n_free + P.n_top;
   q.bot_end = P.n_nodes - P.n_ghost;
   q.dyp = h->d_dy.ptr;
+  q.grip = h->grip;
+  q.vec = !h->grip_default();
   q.nf = P.n_free;
   q.r = pt.r.ptr;
   q.x = pt.x.ptr;
@@ -2532,11 +2548,12 @@ int solve_amg(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opt
       }
       launch_amg_start(s, nd, op, pt.code.ptr, dy_top, dy_bot, v, pt.partials.ptr, tix(pt, 0), pt.red.ptr,
                        pt.amg_lev[0], pt.amg_cg, pt.amg_inv.ptr, o->rtol, o->atol, o->norm, o->max_it, o->reg,
-                       pt.state.ptr, pt.cg_part.ptr, 2 * 4 * kCgMaxPartials);
+                       pt.state.ptr, pt.cg_part.ptr, 2 * 4 * kCgMaxPartials, h->grip_arg());
       ++h->amg_start_fused;
     } else {
       if (!rhs_done)
-        launch_cg_rhs(s, op, pt.code.ptr, dy_top, dy_bot, o->reg, 2, v, pt.partials.ptr, tix(pt, 0), pt.red.ptr);
+        launch_cg_rhs(s, op, pt.code.ptr, dy_top, dy_bot, o->reg, 2, v, pt.partials.ptr, tix(pt, 0), pt.red.ptr,
+                      h->grip_arg());
       if (!start_in_graph)
         launch_cg_init_finalize(s, pt.red.ptr, o->rtol, o->atol, o->norm, o->max_it, o->reg, pt.state.ptr,
                                 pt.cg_part.ptr, 2 * 4 * kCgMaxPartials);
@@ -3508,6 +3525,8 @@ int assemble_impl(mfea_handle* h, mfea_stats* st, const double* rhs_dy = nullptr
       q.bot_end = P.n_nodes - P.n_ghost;
       q.dy_top = rhs_dy[0];
       q.dy_bot = rhs_dy[1];
+      q.grip = h->grip;
+      q.vec = !h->grip_default();
       q.nf = P.n_free;
       q.r = pt.r.ptr;
       q.x = pt.x.ptr;
@@ -3625,9 +3644,16 @@ int enqueue_post_work(mfea_handle* h, double max_strain) {
   for (auto& pp : h->parts) {
     Part& pt = *pp;
     const Pattern& P = pt.P;
-    launch_reaction(s, P.n_free, P.n_top, P.n_nodes, pt.slice_ptr.ptr, pt.row_len.ptr, pt.s_col.ptr,
-                    pt.val.ptr, pt.diag.ptr, pt.G, pt.x.ptr, pt.partials.ptr, tix(pt, 3),
-                    pt.red.ptr + 4);
+    // (other directions than the tensile test's: the reaction vector of the
+    // top rows into red[9..11] and the work-conjugate force into red[4], one launch)
+    if (h->grip_arg())
+      launch_reaction3(s, P.n_free, P.n_top, P.n_nodes, pt.slice_ptr.ptr, pt.row_len.ptr, pt.s_col.ptr, pt.val.ptr,
+                       pt.diag.ptr, pt.G, pt.x.ptr, pt.partials.ptr, tix(pt, 3), pt.red.ptr + 9, h->grip.top,
+                       pt.red.ptr + 4);
+    else
+      launch_reaction(s, P.n_free, P.n_top, P.n_nodes, pt.slice_ptr.ptr, pt.row_len.ptr, pt.s_col.ptr,
+                      pt.val.ptr, pt.diag.ptr, pt.G, pt.x.ptr, pt.partials.ptr, tix(pt, 3),
+                      pt.red.ptr + 4);
     if (dm) HIPC(hipMemsetAsync(pt.fail_cnt.ptr, 0, sizeof(unsigned), s));
     // one partition: the counter is red[6] (read back with the force and the
     // count, no copy of its own), zero here — cleared by the host after the
@@ -3658,7 +3684,8 @@ int enqueue_event_work(mfea_handle* h) {
   hipStream_t s = h->stream;
   Part& pt = part0(h);
   const Pattern& P = pt.P;
-  if ((int64_t)pt.partials.n < event_scan_partials(P.n_top, P.n_elems))
+  const bool vec = !h->grip_default();
+  if ((int64_t)pt.partials.n < event_scan_partials(P.n_top, P.n_elems, vec))
     return fail(MFEA_EINVAL, "internal: partials too small for the event scan");
   double* eps = h->opt_event_scratch ? pt.eps.ptr : nullptr;
   EventScan q{};
@@ -3684,6 +3711,9 @@ int enqueue_event_work(mfea_handle* h) {
   q.cnt_out = pt.red.ptr + 5;
   q.smax_out = pt.red.ptr + 7;
   q.strength = h->strength_d();
+  q.vec = vec;
+  for (int c = 0; c < 3; ++c) q.w[c] = h->grip.top[c];
+  q.sums = pt.red.ptr + 9;
   launch_event_scan(s, q);
   EventApply a{};
   a.E = P.n_elems;
@@ -3966,6 +3996,88 @@ int mfea_set_material(mfea_handle* h, double E, double A, double I) {
   return 0;
 }
 
+// The directions enter the right-hand side, the prescribed rows of x and the
+// reaction only: K, the symbolic hierarchy and the kept values stay.  What
+// holds the old vectors goes: the RHS mfea_step's assembly cached, and every
+// captured graph (the step head and the post hold the vectors and the
+// kernels' GripY / GripVec form by value) — the stream is drained first, so
+// none is in flight.  A z component on a planar mesh changes the lane layout
+// (lane_dofs): the rebuild a layout option takes, the activity kept.
+int mfea_set_grip_motion(mfea_handle* h, const double top[3], const double bot[3]) {
+  if (!h) return fail(MFEA_EINVAL, "NULL handle");
+  // (what the next build will be decides, not the partitions a handle still
+  // holds from before mfea_debug_set_parts(h, 1): those wait for the rebuild)
+  if (h->world > 1 || h->nparts > 1) return fail(MFEA_ESTATE, "mfea_set_grip_motion: one partition per handle");
+  for (const double* v : {top, bot}) {
+    if (!v) continue;
+    if (!std::isfinite(v[0]) || !std::isfinite(v[1]) || !std::isfinite(v[2]))
+      return fail(MFEA_EINVAL, "mfea_set_grip_motion: every component must be finite");
+    if (v[0] == 0.0 && v[1] == 0.0 && v[2] == 0.0)
+      return fail(MFEA_EINVAL, "mfea_set_grip_motion: a direction must not be all zero");
+  }
+  GripVec g = h->grip;
+  for (int c = 0; c < 3; ++c) {
+    // (+ 0.0: a −0 component is stored as 0 — dy · 0 has the sign of dy either way)
+    if (top) g.top[c] = top[c] + 0.0;
+    if (bot) g.bot[c] = bot[c] + 0.0;
+  }
+  if (std::memcmp(&g, &h->grip, sizeof g) == 0) return 0;
+  RC(set_device(h));
+  const int nd0 = lane_dofs(h);
+  if (h->stream) HIPC(hipStreamSynchronize(h->stream));
+  h->grip = g;
+  h->rhs_fused = false;
+  destroy_graph(h);
+  for (auto& gs : h->graph_setup) {
+    if (gs) (void)hipGraphExecDestroy(gs);
+    gs = nullptr;
+  }
+  for (auto& form : h->graph_combo)
+    for (auto& gc : form) {
+      if (gc) (void)hipGraphExecDestroy(gc);
+      gc = nullptr;
+    }
+  if (lane_dofs(h) != nd0) {
+    if (!h->dirty && h->has_mesh && h->Ecount) RC(gather_active(h, h->active_host));
+    h->dirty = true;
+  }
+  return 0;
+}
+
+int mfea_get_grip_motion(mfea_handle* h, double top[3], double bot[3]) {
+  if (!h) return fail(MFEA_EINVAL, "NULL handle");
+  for (int c = 0; c < 3; ++c) {
+    if (top) top[c] = h->grip.top[c];
+    if (bot) bot[c] = h->grip.bot[c];
+  }
+  return 0;
+}
+
+int mfea_get_reaction(mfea_handle* h, double top[3], double bot[3]) {
+  if (!h) return fail(MFEA_EINVAL, "NULL handle");
+  RC(set_device(h));
+  RC(ensure_built(h));
+  if (partitioned(h)) return fail(MFEA_ESTATE, "mfea_get_reaction: one partition per handle");
+  if (!h->assembled) return fail(MFEA_ESTATE, "mfea_get_reaction: no assembly since the last build");
+  Part& pt = part0(h);
+  const Pattern& P = pt.P;
+  hipStream_t s = h->stream;
+  // the two bands are contiguous row ranges: top [n_free, n_free + n_top),
+  // bottom from there to the ghost rows; sums into red[9..11] and red[12..14]
+  const int64_t row0[2] = {P.n_free, P.n_free + P.n_top};
+  const int64_t nrows[2] = {P.n_top, P.n_nodes - P.n_ghost - P.n_free - P.n_top};
+  double* const out[2] = {top, bot};
+  for (int b = 0; b < 2; ++b) {
+    if (!out[b]) continue;
+    launch_reaction3(s, row0[b], nrows[b], P.n_nodes, pt.slice_ptr.ptr, pt.row_len.ptr, pt.s_col.ptr, pt.val.ptr,
+                     pt.diag.ptr, pt.G, pt.x.ptr, pt.partials.ptr, tix(pt, 3), pt.red.ptr + 9 + 3 * b, nullptr,
+                     nullptr);
+    HIPC(hipGetLastError());
+    HIPC(hmemcpy(h, out[b], pt.red.ptr + 9 + 3 * b, 3 * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  return 0;
+}
+
 static bool props_column_ok(const double* v, int64_t n, bool strength) {
   for (int64_t e = 0; v && e < n; ++e) {
     if (strength ? !(v[e] > 0.0) : !(std::isfinite(v[e]) && v[e] >= 0.0)) return false;
@@ -4157,7 +4269,7 @@ static int step_impl(mfea_handle* h, double dy_top, double dy_bot, const mfea_so
     if (fuse_rhs && !(h->opt_amg_start && o.precond == MFEA_PC_GAMG)) {
       Part& pt = part0(h);
       launch_cg_rhs(s, sell_op(pt), pt.code.ptr, dy_top, dy_bot, o.reg, 2, cg_vecs(pt), pt.partials.ptr, tix(pt, 0),
-                    pt.red.ptr);
+                    pt.red.ptr, h->grip_arg());
       HIPC(hipGetLastError());
       h->rhs_fused = true;
       h->rhs_dy[0] = dy_top;

@@ -66,15 +66,20 @@ __device__ __forceinline__ void store3(double* __restrict__ v, int64_t row, cons
 // Free rows: b = 0 − K_fk x_k (only the y DOF of a grip node is nonzero),
 // M⁻¹ from K_ii + reg·I, x = 0, r₀ = b, p = s = 0.  Known rows: x = (0, dy, 0),
 // every Krylov vector and M⁻¹ = 0, so gathers across the boundary read zeros.
+// GM = GripVec (kernels.hpp): known rows x = p = fl(dy · direction), and a
+// known neighbour's whole block, b −= V p (grip_mac).
 // ---------------------------------------------------------------------------
-template <bool BLOCK>
+template <bool BLOCK, class GM>
 __global__ __launch_bounds__(kBlock) void k_cg_rhs(SellOp op, const uint8_t* __restrict__ code,
                                                    double dy_top, double dy_bot, double reg,
                                                    CgVecs v, double* partials, unsigned* ticket,
-                                                   double* red_out) {
+                                                   double* red_out, GM g) {
   const int64_t row = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   double acc[2] = {0.0, 0.0};  // b·b, u₀·u₀
   const double zero[3] = {0.0, 0.0, 0.0};
+  constexpr bool VEC = std::is_same<GM, GripVec>::value;
+  GripP gp{};
+  if constexpr (VEC) gp = grip_disp(g, dy_top, dy_bot);
   if (row < op.nf) {
     const int64_t base = (int64_t)op.slice_ptr[row >> 6] * 64 + (row & 63);
     const int len = op.row_len[row];
@@ -84,10 +89,21 @@ __global__ __launch_bounds__(kBlock) void k_cg_rhs(SellOp op, const uint8_t* __r
       const int64_t idx = base + (int64_t)k * 64;
       const int32_t j = op.s_col[idx];
       if (j >= op.nf && code[j] != 3) {  // a known neighbour (3 = ghost free row: x₀ = 0)
-        const double dy = code[j] == 2 ? dy_bot : dy_top;
-        kx = fma(op.val[1 * G + idx], dy, kx);
-        ky = fma(op.val[3 * G + idx], dy, ky);
-        kz = fma(op.val[4 * G + idx], dy, kz);
+        if constexpr (VEC) {
+          double V[6], pk[3], k3[3] = {kx, ky, kz};
+#pragma unroll
+          for (int c = 0; c < 6; ++c) V[c] = op.val[(int64_t)c * G + idx];
+          grip_of(gp, code[j], pk);
+          grip_mac(V, pk, k3);
+          kx = k3[0];
+          ky = k3[1];
+          kz = k3[2];
+        } else {
+          const double dy = code[j] == 2 ? dy_bot : dy_top;
+          kx = fma(op.val[1 * G + idx], dy, kx);
+          ky = fma(op.val[3 * G + idx], dy, ky);
+          kz = fma(op.val[4 * G + idx], dy, kz);
+        }
       }
     }
     const double b[3] = {0.0 - kx, 0.0 - ky, 0.0 - kz};
@@ -121,7 +137,8 @@ __global__ __launch_bounds__(kBlock) void k_cg_rhs(SellOp op, const uint8_t* __r
     }
   } else if (row < op.N) {
     // ghost free rows (3) hold 0 until the solve's displacement halo fills them
-    const double xk[3] = {0.0, code[row] == 3 ? 0.0 : (code[row] == 2 ? dy_bot : dy_top), 0.0};
+    double xk[3] = {0.0, code[row] == 3 ? 0.0 : (code[row] == 2 ? dy_bot : dy_top), 0.0};
+    if constexpr (VEC) grip_of(gp, code[row], xk);
     store3(v.x, row, xk);
     store3(v.p, row, zero);
     for (int b = 0; b < 2; ++b) {
@@ -146,19 +163,24 @@ __global__ __launch_bounds__(kBlock) void k_cg_rhs(SellOp op, const uint8_t* __r
 // (GAMG stops on the unpreconditioned residual).  A row's slots in batches of
 // four: columns, then their codes, then the known couplings.  b's terms in
 // slot order, as k_cg_rhs.
+template <class GM>
 __global__ __launch_bounds__(kBlock) void k_amg_rhs(SellOp op, const uint8_t* __restrict__ code,
                                                     double dy_top, double dy_bot, CgVecs v,
-                                                    double* partials, unsigned* ticket, double* red_out) {
+                                                    double* partials, unsigned* ticket, double* red_out, GM g) {
   const int64_t row = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   double acc[2] = {0.0, 0.0};
+  constexpr bool VEC = std::is_same<GM, GripVec>::value;
+  GripP gp{};
+  if constexpr (VEC) gp = grip_disp(g, dy_top, dy_bot);
   if (row < op.nf) {
     double b[3];
-    amg_rhs_row(op, code, dy_top, dy_bot, row, b);
+    amg_rhs_row<GM>(op, code, dy_top, dy_bot, row, b, &gp);
     store3(v.r[0], row, b);
 #pragma unroll
     for (int a = 0; a < 3; ++a) acc[0] = fma(b[a], b[a], acc[0]);
   } else if (row < op.N) {
-    const double xk[3] = {0.0, code[row] == 3 ? 0.0 : (code[row] == 2 ? dy_bot : dy_top), 0.0};
+    double xk[3] = {0.0, code[row] == 3 ? 0.0 : (code[row] == 2 ? dy_bot : dy_top), 0.0};
+    if constexpr (VEC) grip_of(gp, code[row], xk);
     store3(v.x, row, xk);
   }
   block_publish<2>(acc, partials, ticket, red_out);
@@ -475,17 +497,29 @@ __global__ void k_cg_advance(int chunk, int shift, Slot* slots, SolveState* st, 
 // ---------------------------------------------------------------------------
 void launch_cg_rhs(hipStream_t s, const SellOp& op, const uint8_t* code, double dy_top,
                    double dy_bot, double reg, int precond, const CgVecs& v, double* partials,
-                   unsigned* ticket, double* red_out) {
+                   unsigned* ticket, double* red_out, const GripVec* grip) {
   const dim3 grid((unsigned)grid_rows(op.N > 0 ? op.N : 1));
+  if (grip) {  // (the directions other than the tensile test's)
+    if (precond == 2)
+      hipLaunchKernelGGL(k_amg_rhs<GripVec>, grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials, ticket,
+                         red_out, *grip);
+    else if (precond == 1)
+      hipLaunchKernelGGL((k_cg_rhs<true, GripVec>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, reg, v,
+                         partials, ticket, red_out, *grip);
+    else
+      hipLaunchKernelGGL((k_cg_rhs<false, GripVec>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, reg, v,
+                         partials, ticket, red_out, *grip);
+    return;
+  }
   if (precond == 2)
-    hipLaunchKernelGGL(k_amg_rhs, grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials, ticket,
-                       red_out);
+    hipLaunchKernelGGL(k_amg_rhs<GripY>, grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials, ticket,
+                       red_out, GripY{});
   else if (precond == 1)
-    hipLaunchKernelGGL(k_cg_rhs<true>, grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, reg, v,
-                       partials, ticket, red_out);
+    hipLaunchKernelGGL((k_cg_rhs<true, GripY>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, reg, v,
+                       partials, ticket, red_out, GripY{});
   else
-    hipLaunchKernelGGL(k_cg_rhs<false>, grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, reg, v,
-                       partials, ticket, red_out);
+    hipLaunchKernelGGL((k_cg_rhs<false, GripY>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, reg, v,
+                       partials, ticket, red_out, GripY{});
 }
 
 void launch_cg_init_finalize(hipStream_t s, const double* red, double rtol, double atol, int norm,

@@ -1,6 +1,8 @@
 // device_util.hpp — device helpers shared by the mfea kernels (wave64 reductions,
 // fence-free sharded last-block finalize, symmetric 3×3 block algebra).
 #pragma once
+#include <type_traits>
+
 #include "kernels.hpp"
 
 namespace mfea {
@@ -170,6 +172,64 @@ __device__ __forceinline__ bool block_publish(double (&v)[NV], double* partials,
   return block_publish_as<NV, BS>(v, partials, ticket, out, gridDim.x, blockIdx.x);
 }
 
+// (K·U)[3·row + c], c = 0..2, of Pattern row `row` on the unregularised K
+// (k_reaction<GripVec>, kernels.hip; k_event_scan<·, GripVec>, events.hip):
+// every block row accumulated as k_reaction accumulates its y row — the
+// diagonal block's three products, then the slots in batches of four, each
+// batch's columns and values issued before its gathers, terms in slot order.
+__device__ __forceinline__ void reaction_row3(int64_t row, int64_t N, const int32_t* __restrict__ slice_ptr,
+                                              const int32_t* __restrict__ row_len,
+                                              const int32_t* __restrict__ s_col, const double* __restrict__ val,
+                                              const double* __restrict__ diag, int64_t G,
+                                              const double* __restrict__ u, double f[3]) {
+  const int64_t base = (int64_t)slice_ptr[row >> 6] * 64 + (row & 63);
+  const int len = row_len[row];
+  {
+    double d[6];
+#pragma unroll
+    for (int c = 0; c < 6; ++c) d[c] = diag[(int64_t)c * N + row];
+    const double u0 = u[3 * row], u1 = u[3 * row + 1], u2 = u[3 * row + 2];
+    f[0] = d[0] * u0 + d[1] * u1 + d[2] * u2;
+    f[1] = d[1] * u0 + d[3] * u1 + d[4] * u2;
+    f[2] = d[2] * u0 + d[4] * u1 + d[5] * u2;
+  }
+  constexpr int U = 4;
+  for (int k0 = 0; k0 < len; k0 += U) {
+    int64_t idx[U], c[U];
+#pragma unroll
+    for (int q = 0; q < U; ++q) {
+      idx[q] = base + (int64_t)(k0 + q < len ? k0 + q : k0) * 64;
+      c[q] = s_col[idx[q]];
+    }
+    double t[U][3];
+#pragma unroll
+    for (int q = 0; q < U; ++q) {
+      double v[6];
+#pragma unroll
+      for (int a = 0; a < 6; ++a) v[a] = val[(int64_t)a * G + idx[q]];
+      const double u0 = u[3 * c[q]], u1 = u[3 * c[q] + 1], u2 = u[3 * c[q] + 2];
+      t[q][0] = v[0] * u0 + v[1] * u1 + v[2] * u2;
+      t[q][1] = v[1] * u0 + v[3] * u1 + v[4] * u2;
+      t[q][2] = v[2] * u0 + v[4] * u1 + v[5] * u2;
+    }
+#pragma unroll
+    for (int q = 0; q < U; ++q)
+      if (k0 + q < len) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) f[a] += t[q][a];
+      }
+  }
+}
+
+// ... reduced over the G blocks into sums[0..2]; the block that ends the
+// reduction forms the work-conjugate force along w into force_out (or NULL):
+//   F = (w[0]·sums[0] + w[1]·sums[1]) + w[2]·sums[2]
+__device__ __forceinline__ void reaction3_publish(double (&f)[3], double* partials, unsigned* ticket, double* sums,
+                                                  const double w[3], double* force_out, unsigned G, unsigned b) {
+  if (!block_publish_as<3>(f, partials, ticket, sums, G, b)) return;
+  if (threadIdx.x == 0 && force_out) *force_out = (w[0] * sums[0] + w[1] * sums[1]) + w[2] * sums[2];
+}
+
 __device__ __forceinline__ void sym_apply(const double B[6], const double v[3], double o[3]) {
   o[0] = fma(B[0], v[0], fma(B[1], v[1], B[2] * v[2]));
   o[1] = fma(B[1], v[0], fma(B[3], v[1], B[4] * v[2]));
@@ -190,15 +250,75 @@ __device__ __forceinline__ void sym_inverse(const double A[6], double B[6]) {
   B[3] = c11 * id; B[4] = c12 * id; B[5] = c22 * id;
 }
 
+// Grip motion (kernels.hpp GripVec): the two prescribed displacements of a
+// launch, p[c] = fl(amplitude · direction[c]) — one product per component
+struct GripP {
+  double top[3], bot[3];
+};
+__device__ __forceinline__ GripP grip_disp(const GripVec& g, double dy_top, double dy_bot) {
+  GripP p;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    p.top[c] = dy_top * g.top[c];
+    p.bot[c] = dy_bot * g.bot[c];
+  }
+  return p;
+}
+// the prescribed displacement of a row of class `code` (1 top, 2 bottom, 3 a
+// ghost free row: 0) — selects on registers, no indexed access
+__device__ __forceinline__ void grip_of(const GripP& p, uint8_t code, double x[3]) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) x[c] = code == 3 ? 0.0 : (code == 2 ? p.bot[c] : p.top[c]);
+}
+// k += V p with V a known neighbour's symmetric block (v0..v5): the RHS term of
+// every GripVec kernel, each row's three terms in component order
+__device__ __forceinline__ void grip_mac(const double v[6], const double p[3], double k[3]) {
+  k[0] = fma(v[2], p[2], fma(v[1], p[1], fma(v[0], p[0], k[0])));
+  k[1] = fma(v[4], p[2], fma(v[3], p[1], fma(v[1], p[0], k[1])));
+  k[2] = fma(v[5], p[2], fma(v[4], p[1], fma(v[2], p[0], k[2])));
+}
+
 // b = 0 − K_fk x_k of free row `row` for the GAMG solves (k_amg_rhs, cg.hip;
 // k_amg_start, amg.hip).  A row's slots in batches of four: columns, then
 // their codes, then the known couplings; b's terms in slot order.
+// GM = GripVec (p: the two prescribed displacements): the whole block, grip_mac.
+template <class GM = GripY>
 __device__ __forceinline__ void amg_rhs_row(const SellOp& op, const uint8_t* __restrict__ code, double dy_top,
-                                            double dy_bot, int64_t row, double b[3]) {
+                                            double dy_bot, int64_t row, double b[3], const GripP* p = nullptr) {
   const int64_t base = (int64_t)op.slice_ptr[row >> 6] * 64 + (row & 63);
   const int len = op.row_len[row];
   const int64_t G = op.G;
   double kx = 0.0, ky = 0.0, kz = 0.0;
+  if constexpr (std::is_same<GM, GripVec>::value) {
+    double k3[3] = {0.0, 0.0, 0.0};
+    constexpr int U = 4;
+    for (int k0 = 0; k0 < len; k0 += U) {
+      int64_t idx[U];
+      int32_t j[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        idx[u] = base + (int64_t)(k0 + u < len ? k0 + u : k0) * 64;
+        j[u] = k0 + u < len ? op.s_col[idx[u]] : 0;
+      }
+      uint8_t c[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) c[u] = k0 + u < len && j[u] >= op.nf ? code[j[u]] : 3;
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if (c[u] != 3) {
+          double v[6], pk[3];
+#pragma unroll
+          for (int q = 0; q < 6; ++q) v[q] = op.val[(int64_t)q * G + idx[u]];
+          grip_of(*p, c[u], pk);
+          grip_mac(v, pk, k3);
+        }
+      }
+    }
+    b[0] = 0.0 - k3[0];
+    b[1] = 0.0 - k3[1];
+    b[2] = 0.0 - k3[2];
+    return;
+  }
   constexpr int U = 4;
   for (int k0 = 0; k0 < len; k0 += U) {
     int64_t idx[U];

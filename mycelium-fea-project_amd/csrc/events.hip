@@ -71,12 +71,21 @@ __device__ __forceinline__ double block_max(double v, double* lds) {
 // (every element block has published by then) takes the max of the block maxima.
 // PS (q.strength): lam_e = max_strain_e / |ε_e| of the same elements and the
 // min in place of the max, through the same publish.
+// GM = GripVec (q.vec): the row blocks run k_reaction<GripVec>'s body — the
+// reaction vector into q.sums, F₁ along q.w into force_out, the same bits.
 // ---------------------------------------------------------------------------
-template <bool PS>
+template <bool PS, class GM>
 __global__ __launch_bounds__(kBlock) void k_event_scan(EventScan q) {
   __shared__ double mx[kBlock / 64];
   if (blockIdx.x < q.grid_r) {
     const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if constexpr (std::is_same<GM, GripVec>::value) {
+      double f3[3] = {0.0, 0.0, 0.0};
+      if (t < q.nrows)
+        reaction_row3(q.row0 + t, q.N, q.slice_ptr, q.row_len, q.s_col, q.val, q.diag, q.G, q.u, f3);
+      reaction3_publish(f3, q.partials_r, q.ticket_r, q.sums, q.w, q.force_out, q.grid_r, blockIdx.x);
+      return;
+    }
     double f[1] = {0.0};
     if (t < q.nrows) {
       const int64_t N = q.N, G = q.G;
@@ -216,14 +225,21 @@ void launch_event_scan(hipStream_t s, EventScan q) {
   q.grid_e = (unsigned)grid_rows(q.E > 0 ? q.E : 1);
   // the two row sets reduce side by side: disjoint partials
   q.partials_r = q.partials;
-  q.partials_e = q.partials_r + (q.grid_r + kShards);
+  q.partials_e = q.partials_r + (q.vec ? 3 : 1) * (q.grid_r + kShards);  // (three sums: three times the room)
   q.pmax = q.partials_e + (q.grid_e + kShards);
-  if (q.strength) hipLaunchKernelGGL(k_event_scan<true>, dim3(q.grid_r + q.grid_e), dim3(kBlock), 0, s, q);
-  else hipLaunchKernelGGL(k_event_scan<false>, dim3(q.grid_r + q.grid_e), dim3(kBlock), 0, s, q);
+  const dim3 g(q.grid_r + q.grid_e);
+  if (q.vec) {
+    if (q.strength) hipLaunchKernelGGL((k_event_scan<true, GripVec>), g, dim3(kBlock), 0, s, q);
+    else hipLaunchKernelGGL((k_event_scan<false, GripVec>), g, dim3(kBlock), 0, s, q);
+    return;
+  }
+  if (q.strength) hipLaunchKernelGGL((k_event_scan<true, GripY>), g, dim3(kBlock), 0, s, q);
+  else hipLaunchKernelGGL((k_event_scan<false, GripY>), g, dim3(kBlock), 0, s, q);
 }
 
-int64_t event_scan_partials(int64_t n_top, int64_t n_elems) {
-  return grid_rows(n_top > 0 ? n_top : 1) + 2 * grid_rows(n_elems > 0 ? n_elems : 1) + 2 * kShards;
+int64_t event_scan_partials(int64_t n_top, int64_t n_elems, bool vec) {
+  return (vec ? 3 : 1) * (grid_rows(n_top > 0 ? n_top : 1) + kShards) + 2 * grid_rows(n_elems > 0 ? n_elems : 1) +
+         kShards;
 }
 
 void launch_event_apply(hipStream_t s, const EventApply& q) {

@@ -76,7 +76,10 @@ __device__ __forceinline__ void bar_block(double vx, double vy, double vz, doubl
 // (EA_e, EI12_e) pairs, kernels.hpp) — a template, not a run-time choice: a
 // selected load would serialise the batch's gathers (below), and the uniform
 // instantiation is the code it was before the pairs existed.
-template <class M>
+// GM: GripY, or GripVec with gp the launch's two prescribed displacements — a
+// known neighbour's whole block then (grip_mac), the class still from the row
+// position and inside the batch as before.
+template <class M, class GM = GripY>
 __device__ __forceinline__ void assemble_row(int64_t N, int64_t row, const double* __restrict__ xyz,
                                              const int32_t* __restrict__ slice_ptr,
                                              const int32_t* __restrict__ row_len,
@@ -84,7 +87,7 @@ __device__ __forceinline__ void assemble_row(int64_t N, int64_t row, const doubl
                                              const int32_t* __restrict__ s_elem,
                                              const uint8_t* __restrict__ active, const M& m,
                                              int64_t G, double* __restrict__ val, double* __restrict__ diag,
-                                             const AsmRhs* q, double* k3) {
+                                             const AsmRhs* q, double* k3, const GripP* gp = nullptr) {
   constexpr bool PE = !std::is_same<M, Material>::value;
   const bool rhs = q != nullptr && row < q->nf;
   const int64_t base = (int64_t)slice_ptr[row >> 6] * 64 + (row & 63);
@@ -149,10 +152,16 @@ __device__ __forceinline__ void assemble_row(int64_t N, int64_t row, const doubl
 #pragma unroll
       for (int c = 0; c < 6; ++c) val[(int64_t)c * G + idx[u]] = v[c];
       if (cd[u] != 3) {  // a known neighbour (3: free or ghost free row, x₀ = 0)
-        const double dy = cd[u] == 2 ? q->dy_bot : q->dy_top;
-        k3[0] = fma(v[1], dy, k3[0]);
-        k3[1] = fma(v[3], dy, k3[1]);
-        k3[2] = fma(v[4], dy, k3[2]);
+        if constexpr (std::is_same<GM, GripVec>::value) {
+          double pk[3];
+          grip_of(*gp, cd[u], pk);
+          grip_mac(v, pk, k3);
+        } else {
+          const double dy = cd[u] == 2 ? q->dy_bot : q->dy_top;
+          k3[0] = fma(v[1], dy, k3[0]);
+          k3[1] = fma(v[3], dy, k3[1]);
+          k3[2] = fma(v[4], dy, k3[2]);
+        }
       }
     }
   }
@@ -259,7 +268,7 @@ __global__ __launch_bounds__(kBlock) void k_diag_rows(int64_t N, const int32_t* 
 
 // RHS: the GAMG solves' RHS too (AsmRhs: k_amg_rhs's outputs from the −S_e
 // blocks in registers) — one launch fewer per step
-template <bool RHS, class M>
+template <bool RHS, class M, class GM = GripY>
 __global__ __launch_bounds__(kBlock) void k_assemble(int64_t N, const double* __restrict__ xyz,
                                                      const int32_t* __restrict__ slice_ptr,
                                                      const int32_t* __restrict__ row_len,
@@ -274,10 +283,13 @@ __global__ __launch_bounds__(kBlock) void k_assemble(int64_t N, const double* __
       q.dy_top = q.dyp[0];
       q.dy_bot = q.dyp[1];
     }
+    constexpr bool VEC = std::is_same<GM, GripVec>::value;
+    GripP gp{};
+    if constexpr (VEC) gp = grip_disp(q.grip, q.dy_top, q.dy_bot);
     double acc[2] = {0.0, 0.0};
     if (row < N) {
       double k3[3] = {0.0, 0.0, 0.0};
-      assemble_row(N, row, xyz, slice_ptr, row_len, s_col, s_elem, active, m, G, val, diag, &q, k3);
+      assemble_row<M, GM>(N, row, xyz, slice_ptr, row_len, s_col, s_elem, active, m, G, val, diag, &q, k3, &gp);
       if (row < q.nf) {
         const double b[3] = {0.0 - k3[0], 0.0 - k3[1], 0.0 - k3[2]};
 #pragma unroll
@@ -286,7 +298,8 @@ __global__ __launch_bounds__(kBlock) void k_assemble(int64_t N, const double* __
         for (int a = 0; a < 3; ++a) acc[0] = fma(b[a], b[a], acc[0]);
       } else {
         const uint8_t c = q.code[row];
-        const double xk[3] = {0.0, c == 3 ? 0.0 : (c == 2 ? q.dy_bot : q.dy_top), 0.0};
+        double xk[3] = {0.0, c == 3 ? 0.0 : (c == 2 ? q.dy_bot : q.dy_top), 0.0};
+        if constexpr (VEC) grip_of(gp, c, xk);
 #pragma unroll
         for (int a = 0; a < 3; ++a) q.x[3 * row + a] = xk[a];
       }
@@ -304,14 +317,18 @@ __global__ __launch_bounds__(kBlock) void k_assemble(int64_t N, const double* __
 // free-row SpMV sees K_fk·p = 0.  Reduces (r·z, b·b, z·z).
 // ---------------------------------------------------------------------------
 
+template <class GM>
 __global__ __launch_bounds__(kBlock) void k_rhs_init(
     int64_t N, int64_t nf, const int32_t* __restrict__ slice_ptr, const int32_t* __restrict__ row_len,
     const int32_t* __restrict__ s_col, const double* __restrict__ val, const double* __restrict__ diag,
     int64_t G, const uint8_t* __restrict__ code, double dy_top, double dy_bot, double reg,
     int precond, double* __restrict__ x, double* __restrict__ r, double* __restrict__ p,
-    double* __restrict__ dinv, double* partials, unsigned* ticket, double* red_out) {
+    double* __restrict__ dinv, double* partials, unsigned* ticket, double* red_out, GM g) {
   const int64_t row = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   double acc[3] = {0.0, 0.0, 0.0};  // r·z, b·b, z·z
+  constexpr bool VEC = std::is_same<GM, GripVec>::value;
+  GripP gp{};
+  if constexpr (VEC) gp = grip_disp(g, dy_top, dy_bot);
   if (row < nf) {
     const int64_t base = (int64_t)slice_ptr[row >> 6] * 64 + (row & 63);
     const int len = row_len[row];
@@ -320,10 +337,21 @@ __global__ __launch_bounds__(kBlock) void k_rhs_init(
       const int64_t idx = base + (int64_t)k * 64;
       const int32_t j = s_col[idx];
       if (j >= nf) {
-        const double dy = code[j] == 2 ? dy_bot : dy_top;  // only the y DOF is nonzero
-        kx = fma(val[1 * G + idx], dy, kx);
-        ky = fma(val[3 * G + idx], dy, ky);
-        kz = fma(val[4 * G + idx], dy, kz);
+        if constexpr (VEC) {  // the whole block: b −= V p
+          double v[6], pk[3], k3[3] = {kx, ky, kz};
+#pragma unroll
+          for (int c = 0; c < 6; ++c) v[c] = val[(int64_t)c * G + idx];
+          grip_of(gp, code[j], pk);
+          grip_mac(v, pk, k3);
+          kx = k3[0];
+          ky = k3[1];
+          kz = k3[2];
+        } else {
+          const double dy = code[j] == 2 ? dy_bot : dy_top;  // only the y DOF is nonzero
+          kx = fma(val[1 * G + idx], dy, kx);
+          ky = fma(val[3 * G + idx], dy, ky);
+          kz = fma(val[4 * G + idx], dy, kz);
+        }
       }
     }
     const double b[3] = {0.0 - kx, 0.0 - ky, 0.0 - kz};  // F_f = 0 − K_fk x_k (py:122)
@@ -353,9 +381,16 @@ __global__ __launch_bounds__(kBlock) void k_rhs_init(
       acc[2] = fma(z[a], z[a], acc[2]);
     }
   } else if (row < N) {
-    x[3 * row] = 0.0;
-    x[3 * row + 1] = code[row] == 2 ? dy_bot : dy_top;
-    x[3 * row + 2] = 0.0;
+    if constexpr (VEC) {
+      double xk[3];
+      grip_of(gp, code[row], xk);
+#pragma unroll
+      for (int a = 0; a < 3; ++a) x[3 * row + a] = xk[a];
+    } else {
+      x[3 * row] = 0.0;
+      x[3 * row + 1] = code[row] == 2 ? dy_bot : dy_top;
+      x[3 * row + 2] = 0.0;
+    }
     p[3 * row] = 0.0; p[3 * row + 1] = 0.0; p[3 * row + 2] = 0.0;
   }
   block_publish<3>(acc, partials, ticket, red_out);
@@ -550,7 +585,13 @@ __global__ void k_advance(int chunk, Slot* slots, SolveState* st) {
 // Reaction: Σ over top grip rows of (K·U)_y with the unregularised K
 // (src/fea_solver.py:252-254, src/fea_petsc.cpp:360-372).  Top rows are a
 // contiguous range of the permutation.
+// GM = GripVec: the reaction vector — all three rows of every block in the
+// same slot order (reaction_row3), three sums through one publish into `sums`,
+// and the work-conjugate force along g.top into red_out (NULL: the sums alone;
+// the bottom band of mfea_get_reaction), formed by the block that ends the
+// reduction: F = (t₀·S₀ + t₁·S₁) + t₂·S₂.
 // ---------------------------------------------------------------------------
+template <class GM>
 __global__ __launch_bounds__(kBlock) void k_reaction(int64_t row0, int64_t nrows, int64_t N,
                                                      const int32_t* __restrict__ slice_ptr,
                                                      const int32_t* __restrict__ row_len,
@@ -558,8 +599,14 @@ __global__ __launch_bounds__(kBlock) void k_reaction(int64_t row0, int64_t nrows
                                                      const double* __restrict__ val,
                                                      const double* __restrict__ diag, int64_t G,
                                                      const double* __restrict__ u, double* partials,
-                                                     unsigned* ticket, double* red_out) {
+                                                     unsigned* ticket, double* red_out, GM g, double* sums) {
   const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if constexpr (std::is_same<GM, GripVec>::value) {
+    double f3[3] = {0.0, 0.0, 0.0};
+    if (t < nrows) reaction_row3(row0 + t, N, slice_ptr, row_len, s_col, val, diag, G, u, f3);
+    reaction3_publish(f3, partials, ticket, sums, g.top, red_out, gridDim.x, blockIdx.x);
+    return;
+  }
   double f[1] = {0.0};
   if (t < nrows) {
     const int64_t row = row0 + t;
@@ -892,7 +939,13 @@ void launch_assemble(hipStream_t s, int64_t N, const double* xyz, const int32_t*
                      const AsmRhs* rhs, const double2* sec) {
   const ElemSection ms{sec};
   if (rhs) {  // (the reduction's blocks publish even when N = 0)
-    if (sec)
+    if (rhs->vec && sec)
+      hipLaunchKernelGGL((k_assemble<true, ElemSection, GripVec>), MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, xyz,
+                         slice_ptr, row_len, s_col, s_elem, active, ms, G, val, diag, *rhs);
+    else if (rhs->vec)
+      hipLaunchKernelGGL((k_assemble<true, Material, GripVec>), MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, xyz,
+                         slice_ptr, row_len, s_col, s_elem, active, m, G, val, diag, *rhs);
+    else if (sec)
       hipLaunchKernelGGL((k_assemble<true, ElemSection>), MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, xyz, slice_ptr,
                          row_len, s_col, s_elem, active, ms, G, val, diag, *rhs);
     else
@@ -940,10 +993,15 @@ void launch_rhs_init(hipStream_t s, int64_t N, int64_t nf, const int32_t* slice_
                      const int32_t* row_len, const int32_t* s_col, const double* val,
                      const double* diag, int64_t G, const uint8_t* code, double dy_top,
                      double dy_bot, double reg, int precond, double* x, double* r, double* p,
-                     double* dinv, double* partials, unsigned* ticket, double* red_out) {
-  hipLaunchKernelGGL(k_rhs_init, MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, nf, slice_ptr, row_len, s_col,
-                     val, diag, G, code, dy_top, dy_bot, reg, precond, x, r, p, dinv, partials,
-                     ticket, red_out);
+                     double* dinv, double* partials, unsigned* ticket, double* red_out, const GripVec* grip) {
+  if (grip)
+    hipLaunchKernelGGL(k_rhs_init<GripVec>, MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, nf, slice_ptr, row_len, s_col,
+                       val, diag, G, code, dy_top, dy_bot, reg, precond, x, r, p, dinv, partials, ticket, red_out,
+                       *grip);
+  else
+    hipLaunchKernelGGL(k_rhs_init<GripY>, MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, nf, slice_ptr, row_len, s_col,
+                       val, diag, G, code, dy_top, dy_bot, reg, precond, x, r, p, dinv, partials,
+                       ticket, red_out, GripY{});
 }
 
 void launch_init_finalize(hipStream_t s, const double* red, double rtol, double atol, int norm,
@@ -989,8 +1047,19 @@ void launch_reaction(hipStream_t s, int64_t row0, int64_t nrows, int64_t N,
                      const int32_t* slice_ptr, const int32_t* row_len, const int32_t* s_col,
                      const double* val, const double* diag, int64_t G, const double* u,
                      double* partials, unsigned* ticket, double* red_out) {
-  hipLaunchKernelGGL(k_reaction, MFEA_GRID(grid_rows(nrows > 0 ? nrows : 1)), row0, nrows, N,
-                     slice_ptr, row_len, s_col, val, diag, G, u, partials, ticket, red_out);
+  hipLaunchKernelGGL(k_reaction<GripY>, MFEA_GRID(grid_rows(nrows > 0 ? nrows : 1)), row0, nrows, N,
+                     slice_ptr, row_len, s_col, val, diag, G, u, partials, ticket, red_out, GripY{},
+                     (double*)nullptr);
+}
+
+void launch_reaction3(hipStream_t s, int64_t row0, int64_t nrows, int64_t N, const int32_t* slice_ptr,
+                      const int32_t* row_len, const int32_t* s_col, const double* val, const double* diag,
+                      int64_t G, const double* u, double* partials, unsigned* ticket, double* sums,
+                      const double* w, double* force_out) {
+  GripVec g{};
+  for (int c = 0; c < 3 && w; ++c) g.top[c] = w[c];
+  hipLaunchKernelGGL(k_reaction<GripVec>, MFEA_GRID(grid_rows(nrows > 0 ? nrows : 1)), row0, nrows, N, slice_ptr,
+                     row_len, s_col, val, diag, G, u, partials, ticket, w ? force_out : nullptr, g, sums);
 }
 
 void launch_stress(hipStream_t s, int64_t E, const int32_t* e2n, const double* xyz,

@@ -94,6 +94,19 @@ struct ElemPost {
   const double* strength;
 };
 
+// Grip motion (mfea_set_grip_motion): the prescribed displacement of a grip
+// node is amplitude · direction, p[c] = fl(dy · dir[c]) — one f64 product per
+// component, formed once per launch (device_util.hpp grip_disp).  GripY: the
+// tensile test, (0, dy, 0) — the kernels as they were before the directions
+// existed.  GripVec: any two directions; a free row's RHS then takes the whole
+// symmetric block of a known neighbour, b −= V·p, and a known row x = p.  The
+// kernels are templates over the two (no run-time choice inside them); a
+// launcher picks GripVec when its `grip` argument is non-null.
+struct GripY {};
+struct GripVec {
+  double top[3], bot[3];
+};
+
 // ---- launchers (defined in kernels.hip) -------------------------------------
 // The GAMG solves' RHS formed in the assembly's row pass (k_amg_rhs's work:
 // b = 0 − K_fk x_k of the free rows into r, the prescribed x of the others,
@@ -102,6 +115,9 @@ struct AsmRhs {
   const uint8_t* code;
   double dy_top, dy_bot;
   const double* dyp;  // non-null: (dy_top, dy_bot) from device memory (a captured step graph)
+  // the grip directions (vec: other than the tensile test's — the GripVec kernel)
+  GripVec grip;
+  bool vec;
   // row classes by position (symbolic.hpp Pattern): top grip rows
   // [nf, top_end), bottom rows [top_end, bot_end), ghost rows after
   int64_t top_end, bot_end;
@@ -135,7 +151,8 @@ void launch_rhs_init(hipStream_t s, int64_t N, int64_t nf, const int32_t* slice_
                      const int32_t* row_len, const int32_t* s_col, const double* val,
                      const double* diag, int64_t G, const uint8_t* code, double dy_top,
                      double dy_bot, double reg, int precond, double* x, double* r, double* p,
-                     double* dinv, double* partials, unsigned* ticket, double* red_out);
+                     double* dinv, double* partials, unsigned* ticket, double* red_out,
+                     const GripVec* grip = nullptr);
 
 void launch_init_finalize(hipStream_t s, const double* red, double rtol, double atol, int norm,
                           int max_it, double reg, Slot* slots, SolveState* st);
@@ -158,6 +175,17 @@ void launch_reaction(hipStream_t s, int64_t row0, int64_t nrows, int64_t N,
                      const int32_t* slice_ptr, const int32_t* row_len, const int32_t* s_col,
                      const double* val, const double* diag, int64_t G, const double* u,
                      double* partials, unsigned* ticket, double* red_out);
+// The reaction vector of a band: sums[c] = Σ over rows [row0, row0 + nrows) of
+// (K·U)[3·row + c], c = x, y, z — every block row accumulated in k_reaction's
+// slot order (the y sum has k_reaction's bits), one launch.  w (or NULL): the
+// band's grip direction; the work-conjugate force
+//   F = (w[0]·sums[0] + w[1]·sums[1]) + w[2]·sums[2]
+// (f64 products and sums in this order, no fused operation) goes to force_out
+// in the same launch.  partials: 3 · (blocks + 8) doubles.
+void launch_reaction3(hipStream_t s, int64_t row0, int64_t nrows, int64_t N, const int32_t* slice_ptr,
+                      const int32_t* row_len, const int32_t* s_col, const double* val, const double* diag,
+                      int64_t G, const double* u, double* partials, unsigned* ticket, double* sums,
+                      const double* w, double* force_out);
 
 // owned (multi-partition): count only elements this partition reports; NULL = all.
 // fail_list / fail_cnt: the (owned) elements that fail in this launch are
@@ -198,9 +226,14 @@ struct EventScan {
   // per-element strength (max_strain_e, or NULL): the scan then reduces
   // min lam_e = max_strain_e / |ε_e| (identity +inf) into smax_out instead
   const double* strength;
+  // vec: the reaction vector of the top rows into sums[0..2] and force_out =
+  // the work-conjugate force along w (launch_reaction3's expression and bits)
+  bool vec;
+  double w[3];
+  double* sums;
 };
 void launch_event_scan(hipStream_t s, EventScan q);
-int64_t event_scan_partials(int64_t n_top, int64_t n_elems);
+int64_t event_scan_partials(int64_t n_top, int64_t n_elems, bool vec = false);
 // k_event_apply: lam = max_strain / *smax, the failing group (activity cleared,
 // event_of = k, appended to fail_list as launch_stress appends), the stress row
 // at the failure load, cnt_out = #active after, lam_out = lam.  eps: the scan's
@@ -262,7 +295,7 @@ void launch_spmv_csr(hipStream_t s, int j, int64_t n, const int64_t* indptr,
 // known rows' x only, u₀·u₀ = 0).
 void launch_cg_rhs(hipStream_t s, const SellOp& op, const uint8_t* code, double dy_top,
                    double dy_bot, double reg, int precond, const CgVecs& v, double* partials,
-                   unsigned* ticket, double* red_out);
+                   unsigned* ticket, double* red_out, const GripVec* grip = nullptr);
 // part: 2 parity buffers × [4][kCgMaxPartials] block partials (cg.hip)
 constexpr int kCgMaxPartials = 512;
 // k_cg_first: w₀ = A u₀; block partials (γ₀, δ₀, r·r, u·u) → part parity 0;

@@ -208,9 +208,38 @@ def read_element_props(path, n_elems):
     return out
 
 
+def parse_grip_direction(text):
+    """``TX,TY,TZ[/BX,BY,BZ]``: the direction of the top grip's motion and, after
+    the slash, of the bottom grip's (without it: the same as the top's, so that
+    the opposite amplitudes of the ramp shear the network along one axis).
+    Returns (top, bot), two float64 arrays of three components
+    (Engine.set_grip_motion's arguments); ValueError names what is wrong."""
+    parts = str(text).split("/")
+    if len(parts) > 2:
+        raise ValueError(f"{text!r}: at most one '/' (TX,TY,TZ[/BX,BY,BZ])")
+    vecs = []
+    for name, part in zip(("top", "bottom"), parts):
+        fields = part.split(",")
+        if len(fields) != 3:
+            raise ValueError(f"{text!r}: the {name} direction needs three components, got {len(fields)}")
+        try:
+            v = np.array([float(f) for f in fields], dtype=np.float64)
+        except ValueError:
+            raise ValueError(f"{text!r}: the {name} direction holds something that is not a number") from None
+        if not np.isfinite(v).all():
+            raise ValueError(f"{text!r}: the {name} direction must be finite")
+        if not v.any():
+            raise ValueError(f"{text!r}: the {name} direction must not be all zero")
+        vecs.append(v)
+    return vecs[0], (vecs[1] if len(vecs) == 2 else vecs[0].copy())
+
+
+TENSILE = (0.0, 1.0, 0.0)
+
+
 def fea_solver(results_dir, tol=GRIP_LENGTH, *, rtol=None, max_it=None, precond=None,
                out_format="python", verbose=True, nparts=1, npy=False, device_run=False,
-               events=False, tie_rtol=1e-9, max_events=None, element_props=None):
+               events=False, tie_rtol=1e-9, max_events=None, element_props=None, grip_direction=None):
     """The reference step loop (src/fea_solver.py:186-335) with the hot path on device.
 
     Reads <results_dir>/nodes.csv + elements.csv, runs N_STEPS load steps and
@@ -248,9 +277,20 @@ def fea_solver(results_dir, tol=GRIP_LENGTH, *, rtol=None, max_it=None, precond=
     (read_element_props) or a dict of per-element arrays E, A, I, max_strain —
     a heterogeneous network (Engine.set_element_props); the columns not given
     stay the module's constants.  Works with the ramp, device_run and events;
-    the record files and their formats do not change."""
+    the record files and their formats do not change.
+
+    grip_direction (one process, one partition): a ``TX,TY,TZ[/BX,BY,BZ]`` string
+    (parse_grip_direction) or a (top, bot) pair of 3-vectors — the grips move
+    along them (Engine.set_grip_motion), dy_top / dy_bot being the amplitudes:
+    a shear or mixed-mode test.  None: the tensile test along y.  Works with the
+    ramp, device_run, events and element_props; force_displacement.csv keeps its
+    two columns, the amplitude span and the work-conjugate force."""
     start_time = time.time()
     rank, world = dist_env()
+    if grip_direction is not None and (world > 1 or nparts > 1):
+        raise ValueError("grip_direction needs one process and one partition (world == 1, nparts == 1)")
+    if isinstance(grip_direction, str):
+        grip_direction = parse_grip_direction(grip_direction)
     if element_props is not None and (world > 1 or nparts > 1):
         raise ValueError("element_props needs one process and one partition (world == 1, nparts == 1)")
     if events and (world > 1 or nparts > 1):
@@ -280,6 +320,8 @@ def fea_solver(results_dir, tol=GRIP_LENGTH, *, rtol=None, max_it=None, precond=
         _join_world(eng, rank, world)
     else:
         eng.set_parts(nparts)
+    if world == 1 and nparts == 1:  # (the process-wide handle keeps its directions: always set)
+        eng.set_grip_motion(*(grip_direction if grip_direction is not None else (TENSILE, TENSILE)))
     eng.set_material(E_mod, A, I)
     eng.set_mesh(coords, e2n)
     eng.set_bc(top, bot)
@@ -449,7 +491,22 @@ def main(argv=None):
     ap.add_argument("--element-props", metavar="FILE", default=None,
                     help="per-element properties: CSV with a header, elem_id plus any of E,A,I,max_strain, "
                          "every element exactly once (one process, one partition)")
+    ap.add_argument("--grip-direction", metavar="TX,TY,TZ[/BX,BY,BZ]", default=None,
+                    help="direction of the grips' motion, the ramp's displacements being the amplitudes "
+                         "(bottom: the same as the top's unless given; one process, one partition); "
+                         "default 0,1,0: the tensile test")
+    ap.add_argument("--shear", action="store_true", help="shorthand for --grip-direction 1,0,0")
     a = ap.parse_args(argv)
+    grip = None
+    if a.shear and a.grip_direction is not None:
+        print("fea_solver: --shear and --grip-direction exclude each other", file=sys.stderr)
+        sys.exit(2)
+    if a.shear or a.grip_direction is not None:
+        try:
+            grip = parse_grip_direction("1,0,0" if a.shear else a.grip_direction)
+        except ValueError as e:
+            print(f"fea_solver: --grip-direction: {e}", file=sys.stderr)
+            sys.exit(2)
     props = None
     if a.element_props is not None:
         try:
@@ -463,7 +520,8 @@ def main(argv=None):
                precond={"gamg": _capi.PC_GAMG, "jacobi": _capi.PC_JACOBI,
                         "bjacobi": _capi.PC_BLOCK_JACOBI, "sor": _capi.PC_SOR, "icc": _capi.PC_ICC}[a.pc],
                out_format=a.format, nparts=a.parts, npy=a.npy, device_run=a.device_run,
-               events=a.events, tie_rtol=a.tie_rtol, max_events=a.max_events, element_props=props)
+               events=a.events, tie_rtol=a.tie_rtol, max_events=a.max_events, element_props=props,
+               grip_direction=grip)
 
 
 if __name__ == "__main__":

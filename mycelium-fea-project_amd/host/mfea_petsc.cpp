@@ -9,7 +9,11 @@
 //              [-ksp_rtol R] [-ksp_atol A] [-ksp_max_it N]
 //              [-ksp_norm_type preconditioned|unpreconditioned]
 //              [-n_steps N] [-disp_max D] [-grip_length G] [-max_strain S]
-//              [-mfea_device K] [-mfea_reg R]
+//              [-mfea_device K] [-mfea_reg R] [-grip_direction tx,ty,tz]
+//
+// -grip_direction: both grips move along (tx, ty, tz) instead of y, the ramp's
+// displacements being the amplitudes (mfea_set_grip_motion; one process) — a
+// shear or mixed-mode test; the force column is the work-conjugate force.
 //
 // Defaults are the reference's: its constants (src/fea_petsc.cpp:23-32) and
 // PETSc's KSP defaults (rtol 1e-5, atol 1e-50, max_it 1e4, the preconditioned
@@ -71,6 +75,8 @@ struct Options {
   double max_strain = 0.018;     // :30
   double grip = 1.5;             // :32
   int device = -1;
+  bool grip_given = false;       // -grip_direction
+  double grip_dir[3] = {0.0, 1.0, 0.0};
 };
 
 [[noreturn]] void die(const std::string& msg) {
@@ -128,6 +134,20 @@ Options parse(int argc, char** argv) {
       o.device = (int)num(v, "-mfea_device");
     } else if (a == "-mfea_reg") {
       o.reg = num(v, "-mfea_reg");
+    } else if (a == "-grip_direction") {
+      std::stringstream ss(v);
+      std::string f;
+      int n = 0;
+      while (std::getline(ss, f, ',')) {
+        if (n == 3) die(std::string("-grip_direction needs three components: ") + v);
+        o.grip_dir[n++] = num(f.c_str(), "-grip_direction");
+      }
+      if (n != 3) die(std::string("-grip_direction needs three components: ") + v);
+      for (double c : o.grip_dir)
+        if (!std::isfinite(c)) die(std::string("-grip_direction must be finite: ") + v);
+      if (o.grip_dir[0] == 0.0 && o.grip_dir[1] == 0.0 && o.grip_dir[2] == 0.0)
+        die("-grip_direction must not be all zero");
+      o.grip_given = true;
     } else {
       die("unknown option " + a);
     }
@@ -144,6 +164,7 @@ void finish_options(Options& o, int world) {
   if (o.precond < 0) o.precond = world > 1 ? MFEA_PC_BLOCK_JACOBI : MFEA_PC_ICC;
   if (world > 1 && (o.precond == MFEA_PC_ICC || o.precond == MFEA_PC_SOR))
     die("-pc_type icc / ilu / sor: one process (use bjacobi, jacobi or gamg under mpirun)");
+  if (world > 1 && o.grip_given) die("-grip_direction: one process");
 }
 
 // src/fea_petsc.cpp:42-82: header skipped, empty lines skipped, the first
@@ -307,6 +328,7 @@ int main(int argc, char** argv) {
     exchange_uid(L, uf ? std::string(uf) : fea_dir + "/.mfea_uid", uid, started);
     check(mfea_dist_init(h, L.rank, L.world, uid), "mfea_dist_init");
   }
+  if (o.grip_given) check(mfea_set_grip_motion(h, o.grip_dir, o.grip_dir), "mfea_set_grip_motion");
   // out-of-range node ids are skipped, as src/fea_petsc.cpp:241 does
   check(mfea_set_mesh(h, N, xyz.data(), E, e2n.data(), MFEA_MESH_SKIP_INVALID), "mfea_set_mesh");
   check(mfea_set_bc(h, (int64_t)top.size(), top.data(), (int64_t)bot.size(), bot.data()),

@@ -118,6 +118,9 @@ _sig = {
     "mfea_set_material": (C.c_int, [_P, C.c_double, C.c_double, C.c_double]),
     "mfea_set_element_props": (C.c_int, [_P, C.POINTER(ElementProps)]),
     "mfea_get_element_props": (C.c_int, [_P, _P, _P, _P, _P]),
+    "mfea_set_grip_motion": (C.c_int, [_P, _P, _P]),
+    "mfea_get_grip_motion": (C.c_int, [_P, _P, _P]),
+    "mfea_get_reaction": (C.c_int, [_P, _P, _P]),
     "mfea_set_mesh": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_uint32]),
     "mfea_set_bc": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P]),
     "mfea_set_active": (C.c_int, [_P, _P]),
@@ -507,6 +510,36 @@ class Engine:
         _check(_lib.mfea_get_element_props(self._h, _ptr(out["E"]), _ptr(out["A"]), _ptr(out["I"]),
                                            _ptr(out["max_strain"])))
         return out
+
+    def set_grip_motion(self, top=None, bot=None):
+        """Directions of the grip motion (mfea_set_grip_motion): a top-band node
+        is prescribed dy_top * top[c], a bottom-band node dy_bot * bot[c];
+        None leaves a direction as it is.  Default (0, 1, 0) for both: the
+        tensile test.  Not normalised."""
+        vecs = []
+        for name, v in (("top", top), ("bot", bot)):
+            if v is None:
+                vecs.append(None)
+                continue
+            a = np.ascontiguousarray(v, dtype=np.float64).ravel()
+            if a.size != 3:
+                raise ValueError(f"{name} must have three components")
+            vecs.append(a)
+        _check(_lib.mfea_set_grip_motion(self._h, *(None if a is None else _ptr(a) for a in vecs)))
+
+    def grip_motion(self):
+        """(top, bot): the two directions (mfea_get_grip_motion)."""
+        top, bot = np.empty(3), np.empty(3)
+        _check(_lib.mfea_get_grip_motion(self._h, _ptr(top), _ptr(bot)))
+        return top, bot
+
+    def reaction(self):
+        """(top3, bot3): per band the sum over its rows of (K U)[3n + c], c = x,
+        y, z, on the unregularised K of the last assembly and the current U
+        (mfea_get_reaction)."""
+        top, bot = np.empty(3), np.empty(3)
+        _check(_lib.mfea_get_reaction(self._h, _ptr(top), _ptr(bot)))
+        return top, bot
 
     def set_bc(self, top, bot):
         top = np.ascontiguousarray(top, dtype=np.int64).ravel()
