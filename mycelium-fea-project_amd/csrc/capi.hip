@@ -21,6 +21,7 @@
 
 #include "amg.hpp"
 #include "amg_kernels.hpp"
+#include "carve.hpp"
 #include "kernels.hpp"
 #include "mfea_debug.h"
 #include "mfea.h"
@@ -502,9 +503,43 @@ unsigned* tix(Part& pt, int k) { return pt.tickets.ptr + (size_t)k * kTicketStri
 // with it, so a fill of the activity could still be landing while the next
 // assembly read it (an intermittent breakdown after set_active(NULL), a
 // K assembled from a mix of the old and the new activity).
+// The lifetime rule of every upload here: the host source of an asynchronous
+// copy lives until the stream sync that follows it — a member, or a local of
+// the frame that syncs, never of an inner block.
 hipError_t hmemcpy(mfea_handle* h, void* dst, const void* src, size_t n, hipMemcpyKind k) {
   const hipError_t e = hipMemcpyAsync(dst, src, n, k, h->stream);
   return e == hipSuccess ? hipStreamSynchronize(h->stream) : e;
+}
+// ... not waited for (nothing to copy: no call)
+hipError_t h2d_async(mfea_handle* h, void* dst, const void* src, size_t bytes) {
+  return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream) : hipSuccess;
+}
+// The index arrays carved from one allocation (carve.hpp).  stage_begin: st
+// has counted them — buf gets that size and the fill pass starts.
+// stage_flush: every array the fill listed goes up, straight from its vector,
+// and the stream is waited for HERE, error or not: the sources (the plan's
+// vectors, locals of the uploader's frame) are free when it returns.
+int stage_begin(DevBuf<int32_t>& buf, IndexStage& st) {
+  HIPC(buf.alloc(std::max<size_t>(st.size(), 1)));
+  st.begin_fill();
+  return 0;
+}
+int stage_flush(mfea_handle* h, DevBuf<int32_t>& buf, const IndexStage& st) {
+  if (st.offset() != st.size() || st.size() > buf.n)
+    return fail(MFEA_EINVAL, "internal: a plan upload's sizing and fill passes differ");
+  hipError_t e = hipSuccess;
+  for (const IndexStage::Item& it : st.items())
+    if (e == hipSuccess) e = h2d_async(h, buf.ptr + it.at, it.v->data(), it.v->size() * sizeof(int32_t));
+  const hipError_t es = hipStreamSynchronize(h->stream);
+  HIPC(e != hipSuccess ? e : es);
+  return 0;
+}
+// Waits for what earlier calls left on the stream (assemblies, activity
+// updates, solves on a current plan) before a plan upload, so that their fault
+// is reported as theirs and not as the upload's first checked call.
+int drain_before_upload(mfea_handle* h, const char* what) {
+  const hipError_t e = hipStreamSynchronize(h->stream);
+  return e == hipSuccess ? 0 : fail(MFEA_EDEVICE, std::string("before ") + what + ": " + hipGetErrorString(e));
 }
 hipError_t hmemset(mfea_handle* h, void* dst, int v, size_t n) {
   const hipError_t e = hipMemsetAsync(dst, v, n, h->stream);
@@ -662,16 +697,17 @@ int upload_part(mfea_handle* h, Part& pt, bool dm) {
   HIPC(pt.slots.alloc(kMaxChunk + 2));
   HIPC(pt.state.alloc(1));
   hipStream_t s = h->stream;
-  auto up = [&](void* d, const void* src, size_t bytes) {
-    return bytes ? hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
-  };
-  HIPC(up(pt.xyz_d.ptr, P.xyz_perm.data(), 3 * N * sizeof(double)));
-  HIPC(up(pt.slice_ptr.ptr, P.slice_ptr.data(), P.slice_ptr.size() * sizeof(int32_t)));
-  HIPC(up(pt.row_len.ptr, P.row_len.data(), N * sizeof(int32_t)));
-  HIPC(up(pt.s_col.ptr, P.s_col.data(), pt.G * sizeof(int32_t)));
-  HIPC(up(pt.s_elem.ptr, P.s_elem.data(), pt.G * sizeof(int32_t)));
-  HIPC(up(pt.e2n_d.ptr, P.e2n_perm.data(), 2 * E * sizeof(int32_t)));
-  HIPC(up(pt.code.ptr, P.code.data(), N * sizeof(uint8_t)));
+  // the host sources built here: alive until the sync at the end (hmemcpy's rule)
+  std::vector<uint8_t> act;
+  std::vector<uint32_t> code;
+  std::vector<int32_t> push, rs, rr;
+  HIPC(h2d_async(h, pt.xyz_d.ptr, P.xyz_perm.data(), 3 * N * sizeof(double)));
+  HIPC(h2d_async(h, pt.slice_ptr.ptr, P.slice_ptr.data(), P.slice_ptr.size() * sizeof(int32_t)));
+  HIPC(h2d_async(h, pt.row_len.ptr, P.row_len.data(), N * sizeof(int32_t)));
+  HIPC(h2d_async(h, pt.s_col.ptr, P.s_col.data(), pt.G * sizeof(int32_t)));
+  HIPC(h2d_async(h, pt.s_elem.ptr, P.s_elem.data(), pt.G * sizeof(int32_t)));
+  HIPC(h2d_async(h, pt.e2n_d.ptr, P.e2n_perm.data(), 2 * E * sizeof(int32_t)));
+  HIPC(h2d_async(h, pt.code.ptr, P.code.data(), N * sizeof(uint8_t)));
   HIPC(hipMemsetAsync(pt.tickets.ptr, 0, kTicketSets * kTicketStride * sizeof(unsigned), s));
   HIPC(hipMemsetAsync(pt.red.ptr, 0, 16 * sizeof(double), s));
   HIPC(hipMemsetAsync(pt.x.ptr, 0, 3 * N * sizeof(double), s));
@@ -680,7 +716,6 @@ int upload_part(mfea_handle* h, Part& pt, bool dm) {
   HIPC(hipMemsetAsync(pt.stress.ptr, 0, E * sizeof(double), s));
   HIPC(hipMemsetAsync(pt.val.ptr, 0, 6 * pt.G * sizeof(double), s));
   HIPC(hipMemsetAsync(pt.diag.ptr, 0, 6 * N * sizeof(double), s));
-  std::vector<uint8_t> act;
   if (h->active_host.size() == (size_t)h->Ecount) {
     if (dm) {
       act.resize(E);
@@ -688,7 +723,7 @@ int upload_part(mfea_handle* h, Part& pt, bool dm) {
     } else {
       act = h->active_host;
     }
-    HIPC(up(pt.active.ptr, act.data(), E));
+    HIPC(h2d_async(h, pt.active.ptr, act.data(), E));
   } else {
     HIPC(hipMemsetAsync(pt.active.ptr, 1, E, s));
   }
@@ -700,7 +735,7 @@ int upload_part(mfea_handle* h, Part& pt, bool dm) {
   if (pt.ell_ok) {
     const Ell& L = pt.L;
     const int64_t NL = L.n_lanes;
-    std::vector<uint32_t> code(NL);
+    code.resize(NL);
     for (int64_t l = 0; l < NL; ++l)
       code[l] = (L.code[l] & 0xFFFFFFu) | (uint32_t)(uint8_t)(int8_t)L.info[l] << 24;
     HIPC(pt.e_code.alloc(NL));
@@ -709,23 +744,23 @@ int upload_part(mfea_handle* h, Part& pt, bool dm) {
     HIPC(pt.e_src_pos.alloc(3 * NL));
     HIPC(pt.e_nbr_lane.alloc(3 * NL));
     HIPC(pt.e_f.alloc((kEllDoubles - 24) * NL + 24 * std::max<int64_t>(NL, L.n_hrec + 1)));
-    HIPC(up(pt.e_code.ptr, code.data(), NL * sizeof(uint32_t)));
+    HIPC(h2d_async(h, pt.e_code.ptr, code.data(), NL * sizeof(uint32_t)));
     // Halo record layout (ell.hip load_lane): compact (measured on one box:
     // C3 21.8 vs 23.7 µs per iteration, C2 41.6 vs 41.7 ms per step) or one
     // per lane (option "ell_compact" 0).  The device partner is the record the lane
     // fills: its mirror lane's record.
     pt.ell_hc = h->opt_ell_compact;
-    std::vector<int32_t> push(NL);
+    push.resize(NL);
     for (int64_t l = 0; l < NL; ++l)
       push[l] = L.partner[l] >= 0 ? (pt.ell_hc ? L.hrec[L.partner[l]] : L.partner[l]) : L.partner[l];
-    HIPC(up(pt.e_partner.ptr, push.data(), NL * sizeof(int32_t)));
+    HIPC(h2d_async(h, pt.e_partner.ptr, push.data(), NL * sizeof(int32_t)));
     HIPC(pt.e_hmask.alloc(NL / 64));
     HIPC(pt.e_hbase.alloc(NL / 64));
-    HIPC(up(pt.e_hmask.ptr, L.hmask.data(), NL / 64 * sizeof(uint64_t)));
-    HIPC(up(pt.e_hbase.ptr, L.hbase.data(), NL / 64 * sizeof(int32_t)));
-    HIPC(up(pt.e_lane_row.ptr, L.lane_row.data(), NL * sizeof(int32_t)));
-    HIPC(up(pt.e_src_pos.ptr, L.src_pos.data(), 3 * NL * sizeof(int32_t)));
-    HIPC(up(pt.e_nbr_lane.ptr, L.nbr_lane.data(), 3 * NL * sizeof(int32_t)));
+    HIPC(h2d_async(h, pt.e_hmask.ptr, L.hmask.data(), NL / 64 * sizeof(uint64_t)));
+    HIPC(h2d_async(h, pt.e_hbase.ptr, L.hbase.data(), NL / 64 * sizeof(int32_t)));
+    HIPC(h2d_async(h, pt.e_lane_row.ptr, L.lane_row.data(), NL * sizeof(int32_t)));
+    HIPC(h2d_async(h, pt.e_src_pos.ptr, L.src_pos.data(), 3 * NL * sizeof(int32_t)));
+    HIPC(h2d_async(h, pt.e_nbr_lane.ptr, L.nbr_lane.data(), 3 * NL * sizeof(int32_t)));
     // zero records: a lane without a halo slot reads its neighbour's (unused)
     if (NL) HIPC(hipMemsetAsync(pt.e_f.ptr, 0, pt.e_f.n * sizeof(double), s));
   }
@@ -749,15 +784,16 @@ int upload_part(mfea_handle* h, Part& pt, bool dm) {
     HIPC(pt.xh.alloc(3 * (ns + nr)));
     pt.xh_send = pt.xh.ptr;
     pt.xh_recv = pt.xh.ptr + 3 * ns;
-    std::vector<int32_t> rs(ns), rr(nr);
+    rs.resize(ns);
+    rr.resize(nr);
     for (int64_t i = 0; i < ns; ++i) rs[i] = P.iperm[pl.xsend_node[i]];
     for (int64_t i = 0; i < nr; ++i) rr[i] = P.iperm[pl.xrecv_node[i]];
     HIPC(pt.xsend_rows.alloc(ns));
     HIPC(pt.xrecv_rows.alloc(nr));
-    HIPC(up(pt.xsend_rows.ptr, rs.data(), ns * sizeof(int32_t)));
-    HIPC(up(pt.xrecv_rows.ptr, rr.data(), nr * sizeof(int32_t)));
+    HIPC(h2d_async(h, pt.xsend_rows.ptr, rs.data(), ns * sizeof(int32_t)));
+    HIPC(h2d_async(h, pt.xrecv_rows.ptr, rr.data(), nr * sizeof(int32_t)));
     HIPC(pt.elem_own.alloc(E));
-    HIPC(up(pt.elem_own.ptr, pl.elem_own.data(), E));
+    HIPC(h2d_async(h, pt.elem_own.ptr, pl.elem_own.data(), E));
   }
   HIPC(pt.fail_list.alloc(std::max<int64_t>(E, 1)));
   HIPC(pt.fail_cnt.alloc(1));
@@ -1375,9 +1411,6 @@ int solve_impl(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_op
 // ---------------------------------------------------------------------------
 // SA-AMG preconditioned CG (amg.hpp / amg.hip), single partition.
 // ---------------------------------------------------------------------------
-constexpr size_t kAmgAlign = 64;  // elements: every carved array starts 256/512-B aligned
-size_t amg_al(size_t n) { return (n + kAmgAlign - 1) / kAmgAlign * kAmgAlign; }
-
 // rows [lo, hi) of a SELL pattern and their positions (amg_kernels.hpp RowRange)
 RowRange row_range(const SellPat& S, int64_t lo, int64_t hi) {
   RowRange g;
@@ -1394,7 +1427,8 @@ RowRange row_range(const SellPat& S, int64_t lo, int64_t hi) {
 }
 
 // Carves the plan's index arrays and the value / vector arrays out of two
-// device allocations and uploads the indices.  Pass 0 sizes, pass 1 carves.
+// device allocations and uploads the indices (carve.hpp, stage_flush).  Pass 0
+// sizes, pass 1 carves.
 // rk (distributed GAMG): this partition's row ranges, with its own level-0
 // lists over ITS pattern (a0, row0) in place of the plan's.
 // strength of connection of the level-0 aggregation (option amg_theta_ppm;
@@ -1534,7 +1568,7 @@ int upload_amg(mfea_handle* h, Part& pt, const AmgPlan& pl, const AmgRank* rk = 
   const int nd = pl.nd, nb2 = nd * nd;
   const int nlev = (int)pl.lev.size();
   hipStream_t s = h->stream;
-  size_t ni = 0, ndd = 0, nff = 0;
+  size_t ndd = 0, nff = 0;
   pt.amg_coll = AmgCollapse();
   // (a distributed plan: collapsed among its replicated levels only)
   if ((!rk || rk->compact) && h->opt_amg_cycle == 1 && h->opt_amg_collapse != 0) {
@@ -1572,54 +1606,39 @@ int upload_amg(mfea_handle* h, Part& pt, const AmgPlan& pl, const AmgRank* rk = 
     row0_inv.assign(pl.row0.size(), -1);
     for (size_t i = 0; i < pl.row0.size(); ++i) row0_inv[pl.row0[i]] = (int32_t)i;
   }
-  int32_t* ip = nullptr;
-  double* dp = nullptr;
-  float* fp = nullptr;
+  IndexStage ist(kAmgAlign);  // pt.amg_i's arrays: pass 1 lists their copies, stage_flush issues them
   int pass = 0;
-  hipError_t err = hipSuccess;
   auto I = [&](const std::vector<int32_t>& v) -> const int32_t* {
-    if (pass == 0) {
-      ni += amg_al(v.size());
-      return nullptr;
-    }
-    int32_t* p = ip;
-    ip += amg_al(v.size());
-    if (!v.empty() && err == hipSuccess)
-      err = hipMemcpyAsync(p, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice, s);
-    return p;
+    const size_t at = ist.put(v);
+    return pass == 0 ? nullptr : pt.amg_i.ptr + at;
   };
-  auto D = [&](size_t n) -> double* {
-    if (pass == 0) {
-      ndd += amg_al(n);
-      return nullptr;
-    }
-    double* p = dp;
-    dp += amg_al(n);
-    return p;
+  // (ndd, nff: the running offsets into amg_d and amg_f, pass 0's totals)
+  auto carve = [&](auto* base, size_t& end, size_t n) {
+    const size_t at = end;
+    end += amg_al(n);
+    return pass == 0 ? nullptr : base + at;
   };
-  auto F = [&](size_t n) -> float* {
-    if (pass == 0) {
-      nff += amg_al(n);
-      return nullptr;
-    }
-    float* p = fp;
-    fp += amg_al(n);
-    return p;
-  };
+  auto D = [&](size_t n) { return carve(pt.amg_d.ptr, ndd, n); };
+  auto F = [&](size_t n) { return carve(pt.amg_f.ptr, nff, n); };
   // vals64: f64 values, vals32: f32 values (the numeric setup stores every
   // hierarchy value in f32 — computing in f64 — and the V-cycle reads them;
   // only A_0's symmetric blocks for the CG's w = A u stay f64)
-  std::deque<std::vector<int32_t>> srows;  // alive until the copies below have run (the stream sync at the end)
+  std::deque<std::vector<int32_t>> srows;  // built in pass 1, alive until stage_flush has run
   auto mat = [&](const SellPat& S, bool vals64, bool vals32) {
     AmgMatD m;
     m.n = S.n;
     m.npos = S.n_pos();
     for (size_t k = 0; k + 1 < S.sptr.size(); ++k) m.wmax = std::max(m.wmax, S.sptr[k + 1] - S.sptr[k]);
     m.sptr = I(S.sptr);
-    std::vector<int32_t>& srow = srows.emplace_back(S.sptr.empty() ? 0 : S.sptr.back(), 0);  // slot row → slice
-    for (size_t k = 0; k + 1 < S.sptr.size(); ++k)
-      for (int32_t t = S.sptr[k]; t < S.sptr[k + 1]; ++t) srow[t] = (int32_t)k;
-    m.srow = I(srow);
+    const size_t nrow = S.sptr.empty() ? 0 : S.sptr.back();
+    if (pass == 0) {
+      ist.reserve(nrow);
+    } else {
+      std::vector<int32_t>& srow = srows.emplace_back(nrow, 0);  // slot row → slice
+      for (size_t k = 0; k + 1 < S.sptr.size(); ++k)
+        for (int32_t t = S.sptr[k]; t < S.sptr[k + 1]; ++t) srow[t] = (int32_t)k;
+      m.srow = I(srow);
+    }
     m.col = I(S.col);
     m.val = vals64 ? D((size_t)nb2 * m.npos) : nullptr;
     m.val32 = vals32 ? F((size_t)nb2 * m.npos) : nullptr;
@@ -1627,14 +1646,12 @@ int upload_amg(mfea_handle* h, Part& pt, const AmgPlan& pl, const AmgRank* rk = 
   };
   for (pass = 0; pass < 2; ++pass) {
     if (pass == 1) {
-      HIPC(pt.amg_i.alloc(std::max<size_t>(ni, 1)));
+      RC(stage_begin(pt.amg_i, ist));
       HIPC(pt.amg_d.alloc(std::max<size_t>(ndd, 1)));
       HIPC(pt.amg_f.alloc(std::max<size_t>(nff, 1)));
       HIPC(hipMemsetAsync(pt.amg_d.ptr, 0, pt.amg_d.n * sizeof(double), s));
       HIPC(hipMemsetAsync(pt.amg_f.ptr, 0, pt.amg_f.n * sizeof(float), s));
-      ip = pt.amg_i.ptr;
-      dp = pt.amg_d.ptr;
-      fp = pt.amg_f.ptr;
+      ndd = nff = 0;
     }
     pt.amg_lev.assign(nlev, AmgLevD{});
     for (int l = 0; l < nlev; ++l) {
@@ -1780,7 +1797,7 @@ int upload_amg(mfea_handle* h, Part& pt, const AmgPlan& pl, const AmgRank* rk = 
       g.B = F((size_t)nd * (M.n1 + 2 * M.n2 + 1));
     }
   }
-  HIPC(err);
+  RC(stage_flush(h, pt.amg_i, ist));
   pt.amg_x2 = nlev > 2 ? pt.amg_lev[2].x : nullptr;
   pt.amg_e2 = nlev > 2 ? pt.amg_lev[2].e : nullptr;
   set_merge(h, pt);
@@ -1828,19 +1845,21 @@ int upload_amg_halo(mfea_handle* h, Part& pt, const std::vector<uint8_t>& key) {
   if (!err.empty()) return fail(MFEA_EINVAL, "AMG halo: " + err);
   const AmgHalo& hl = pt.amg_halo;
   const int nd = pt.amg.nd;
-  const size_t a = hl.send_rows.size(), b = hl.gptr.size(), c = hl.gslot.size();
-  HIPC(pt.amg_hi.alloc(a + b + 2 * c + 1));
-  HIPC(pt.amg_hd.alloc(nd * (xs.size() + xr.size()) + 1));
   hipStream_t s = h->stream;
-  auto up = [&](int32_t* d, const std::vector<int32_t>& v) {
-    return v.empty() ? hipSuccess : hipMemcpyAsync(d, v.data(), v.size() * 4, hipMemcpyHostToDevice, s);
-  };
-  int32_t* ib = pt.amg_hi.ptr;
-  HIPC(up(ib, hl.send_rows));
-  HIPC(up(ib + a, hl.gptr));
-  HIPC(up(ib + a + b, hl.gslot));
-  HIPC(up(ib + a + b + c, hl.grecv));
+  HIPC(pt.amg_hd.alloc(nd * (xs.size() + xr.size()) + 1));
   HIPC(hipMemsetAsync(pt.amg_hd.ptr, 0, pt.amg_hd.n * sizeof(double), s));
+  IndexStage st;
+  size_t send_rows = 0, gptr = 0, gslot = 0, grecv = 0;
+  for (int pass = 0; pass < 2; ++pass) {  // count, then fill
+    if (pass == 1) RC(stage_begin(pt.amg_hi, st));
+    send_rows = st.put(hl.send_rows);
+    gptr = st.put(hl.gptr);
+    gslot = st.put(hl.gslot);
+    grecv = st.put(hl.grecv);
+    st.reserve(1);  // (an empty last list still points inside)
+  }
+  RC(stage_flush(h, pt.amg_hi, st));
+  const int32_t* ib = pt.amg_hi.ptr;
   AmgDist& d = pt.amg_dist;
   d = AmgDist{};
   d.rank = pt.rank;
@@ -1848,16 +1867,15 @@ int upload_amg_halo(mfea_handle* h, Part& pt, const std::vector<uint8_t>& key) {
   d.gall[1] = pt.dv.gall[1];
   d.gsend = pt.dv.gsend;
   d.zero_w = h->world > 1 && h->opt_dist_sums == 1 ? h->world : 0;
-  d.send_rows = ib;
-  d.n_send = (int64_t)a;
-  d.gptr = ib + a;
-  d.gslot = ib + a + b;
-  d.grecv = ib + a + b + c;
+  d.send_rows = ib + send_rows;
+  d.n_send = (int64_t)hl.send_rows.size();
+  d.gptr = ib + gptr;
+  d.gslot = ib + gslot;
+  d.grecv = ib + grecv;
   d.sval = pt.val.ptr;
   d.G = pt.G;
   d.usend = pt.amg_hd.ptr;
   d.urecv = pt.amg_hd.ptr + nd * xs.size();
-  HIPC(hipStreamSynchronize(s));
   return 0;
 }
 
@@ -1888,50 +1906,44 @@ int upload_sweep(mfea_handle* h, Part& pt, int kind) {
   if (sp.colors > kSweepMaxColors) return fail(MFEA_EINVAL, "sweep plan: too many colours");
   const int nd = pt.amg.nd, nb2 = nd * nd, ns = nd * (nd + 1) / 2;
   const int64_t ne = sp.n_entries();
-  const std::vector<int32_t>* iv[] = {&sp.wsteps, &sp.row, &sp.ppos, &sp.dpos, &sp.lo_ptr,
-                                      &sp.lo_ent, &sp.lo_pos, &sp.up_ptr, &sp.up_ent, &sp.up_pos};
-  size_t ni = 1;
-  for (auto* v : iv) ni += v->size();
-  HIPC(pt.sw_i.alloc(ni));
   const size_t nlo = sp.lo_ent.size(), nup = sp.up_ent.size();
   HIPC(pt.sw_f.alloc((size_t)ne * (nb2 + ns) + (nlo + nup) * nb2 + 1));
   HIPC(pt.sw_y.alloc((size_t)ne * nd + 1));
-  int32_t* ip = pt.sw_i.ptr;
   hipStream_t s = h->stream;
-  auto put = [&](const std::vector<int32_t>& v) -> const int32_t* {
-    int32_t* p = ip;
-    if (!v.empty()) (void)hipMemcpyAsync(p, v.data(), v.size() * 4, hipMemcpyHostToDevice, s);
-    ip += v.size();
-    return p;
-  };
+  // pads and first steps are never written by the setup: zero them once
+  HIPC(hipMemsetAsync(pt.sw_f.ptr, 0, pt.sw_f.n * sizeof(float), s));
+  HIPC(hipMemsetAsync(pt.sw_y.ptr, 0, pt.sw_y.n * sizeof(double), s));
   SweepD& w = pt.swd;
+  // the index arrays and their pointers, one after the other in sw_i
+  struct Arr {
+    const std::vector<int32_t>* v;
+    const int32_t** d;
+  };
+  const Arr arr[] = {{&sp.wsteps, &w.wsteps}, {&sp.row, &w.row},       {&sp.ppos, &w.ppos},     {&sp.dpos, &w.dpos},
+                     {&sp.lo_ptr, &w.lo_ptr}, {&sp.lo_ent, &w.lo_ent}, {&sp.lo_pos, &w.lo_pos}, {&sp.up_ptr, &w.up_ptr},
+                     {&sp.up_ent, &w.up_ent}, {&sp.up_pos, &w.up_pos}};
+  IndexStage st;
+  for (int pass = 0; pass < 2; ++pass) {  // count, then fill
+    if (pass == 1) RC(stage_begin(pt.sw_i, st));
+    for (const Arr& a : arr) {
+      const size_t at = st.put(*a.v);
+      if (pass == 1) *a.d = pt.sw_i.ptr + at;
+    }
+    st.reserve(1);  // (an empty last list still points inside)
+  }
+  RC(stage_flush(h, pt.sw_i, st));
   w.n = sp.n;
   w.ne = ne;
   w.colors = sp.colors;
   w.dic = kind == MFEA_PC_ICC ? 1 : 0;
   for (int c = 0; c <= sp.colors; ++c) w.cw[c] = sp.cwave[c];
-  w.wsteps = put(sp.wsteps);
-  w.row = put(sp.row);
-  w.ppos = put(sp.ppos);
-  w.dpos = put(sp.dpos);
-  w.lo_ptr = put(sp.lo_ptr);
-  w.lo_ent = put(sp.lo_ent);
-  w.lo_pos = put(sp.lo_pos);
-  w.up_ptr = put(sp.up_ptr);
-  w.up_ent = put(sp.up_ent);
-  w.up_pos = put(sp.up_pos);
   float* fp = pt.sw_f.ptr;
   w.pv = fp;
   w.dt = fp + (size_t)ne * nb2;
   w.lov = w.dt + (size_t)ne * ns;
   w.upv = w.lov + nlo * nb2;
-  // pads and first steps are never written by the setup: zero them once
-  HIPC(hipMemsetAsync(fp, 0, pt.sw_f.n * sizeof(float), s));
   w.y = pt.sw_y.ptr;
-  HIPC(hipMemsetAsync(w.y, 0, pt.sw_y.n * sizeof(double), s));
   pt.amg_cg.sweep = 1;
-  HIPC(hipGetLastError());
-  HIPC(hipStreamSynchronize(s));
   return 0;
 }
 
@@ -2062,6 +2074,7 @@ int ensure_amg(mfea_handle* h, Part& pt, bool* rebuilt, int kind = MFEA_PC_GAMG)
   if (pt.amg_ok && pt.amg_key == key) {
     if (!dm) pt.amg_seen_gen = h->act_gen;
     if (!dm || pt.dev_plan == 0) return 0;
+    RC(drain_before_upload(h, "plan upload"));
     destroy_graph(h);  // the device holds the global plan: upload this one again
     RC(upload_amg(h, pt, pt.amg));
     RC(upload_amg_halo(h, pt, key));
@@ -2082,6 +2095,8 @@ int ensure_amg(mfea_handle* h, Part& pt, bool* rebuilt, int kind = MFEA_PC_GAMG)
   if (err.empty() && sweep) err = build_sweep_bounded(pt.amg, h->opt_sweep_piece, pt.sweep);
   if (!err.empty()) return fail(MFEA_EINVAL, "AMG setup: " + err);
   clk.lap("plan build");
+  RC(drain_before_upload(h, "plan upload"));
+  clk.lap("drain");
   destroy_graph(h);
   pt.amg_kind = kind;
   RC(upload_amg(h, pt, pt.amg));
@@ -2812,55 +2827,41 @@ int global_active(mfea_handle* h, std::vector<uint8_t>& key) {
 int upload_xplans(mfea_handle* h, Part& pt) {
   const AmgRank& rk = pt.amg_rank;
   const int nd = h->gamg.nd;
-  size_t items = 0, stage = 1;
-  auto size = [&](const XPlan& x, int width_bytes) {
-    items += x.sidx.size() + x.ridx.size() + 2;
+  size_t stage = 1;
+  IndexStage st(1, /*gap=*/1);  // (the gap: empty lists get offsets of their own)
+  int pass = 0;
+  auto put = [&](const XPlan& x, int width_bytes) -> Part::XDev {
     stage = std::max(stage, (size_t)std::max(x.n_send(), x.n_recv()) * width_bytes);
-  };
-  for (const auto& x : rk.xa) size(x, 4 * nd);
-  for (const auto& x : rk.xr) size(x, 4 * nd);
-  for (const auto& x : rk.xp) size(x, 4 * nd);
-  size(rk.xg, 4 * nd);
-  for (const auto& x : rk.sp) size(x, 8 * nd * nd);
-  for (const auto& x : rk.sap) size(x, 8 * nd * nd);
-  size(rk.sg, 8 * nd * nd);
-  size(rk.xc, 4 * nd);
-  size(rk.spt, 4 * nd * nd);
-  size(rk.sd, 4 * nd * nd);
-  HIPC(pt.amg_xi.alloc(items));
-  HIPC(pt.amg_xs.alloc(stage / 8 + 1));
-  HIPC(pt.amg_xr.alloc(stage / 8 + 1));
-  int32_t* ip = pt.amg_xi.ptr;
-  hipStream_t s = h->stream;
-  auto put = [&](const XPlan& x) -> Part::XDev {
+    const size_t s = st.put(x.sidx), r = st.put(x.ridx);
     Part::XDev d;
     d.x = &x;
-    d.s = ip;
-    if (!x.sidx.empty()) (void)hipMemcpyAsync(ip, x.sidx.data(), x.sidx.size() * 4, hipMemcpyHostToDevice, s);
-    ip += x.sidx.size() + 1;
-    d.r = ip;
-    if (!x.ridx.empty()) (void)hipMemcpyAsync(ip, x.ridx.data(), x.ridx.size() * 4, hipMemcpyHostToDevice, s);
-    ip += x.ridx.size() + 1;
+    d.s = pass == 0 ? nullptr : pt.amg_xi.ptr + s;
+    d.r = pass == 0 ? nullptr : pt.amg_xi.ptr + r;
     return d;
   };
-  pt.xd_a.clear();
-  pt.xd_r.clear();
-  pt.xd_p.clear();
-  pt.xd_sp.clear();
-  pt.xd_sap.clear();
-  for (const auto& x : rk.xa) pt.xd_a.push_back(put(x));
-  for (const auto& x : rk.xr) pt.xd_r.push_back(put(x));
-  for (const auto& x : rk.xp) pt.xd_p.push_back(put(x));
-  pt.xd_g = put(rk.xg);
-  for (const auto& x : rk.sp) pt.xd_sp.push_back(put(x));
-  for (const auto& x : rk.sap) pt.xd_sap.push_back(put(x));
-  pt.xd_sg = put(rk.sg);
-  pt.xd_c = put(rk.xc);
-  pt.xd_spt = put(rk.spt);
-  pt.xd_sd = put(rk.sd);
-  HIPC(hipGetLastError());
-  HIPC(hipStreamSynchronize(s));
-  return 0;
+  for (pass = 0; pass < 2; ++pass) {  // count, then fill
+    if (pass == 1) {
+      RC(stage_begin(pt.amg_xi, st));
+      HIPC(pt.amg_xs.alloc(stage / 8 + 1));
+      HIPC(pt.amg_xr.alloc(stage / 8 + 1));
+    }
+    pt.xd_a.clear();
+    pt.xd_r.clear();
+    pt.xd_p.clear();
+    pt.xd_sp.clear();
+    pt.xd_sap.clear();
+    for (const auto& x : rk.xa) pt.xd_a.push_back(put(x, 4 * nd));
+    for (const auto& x : rk.xr) pt.xd_r.push_back(put(x, 4 * nd));
+    for (const auto& x : rk.xp) pt.xd_p.push_back(put(x, 4 * nd));
+    pt.xd_g = put(rk.xg, 4 * nd);
+    for (const auto& x : rk.sp) pt.xd_sp.push_back(put(x, 8 * nd * nd));
+    for (const auto& x : rk.sap) pt.xd_sap.push_back(put(x, 8 * nd * nd));
+    pt.xd_sg = put(rk.sg, 8 * nd * nd);
+    pt.xd_c = put(rk.xc, 4 * nd);
+    pt.xd_spt = put(rk.spt, 4 * nd * nd);
+    pt.xd_sd = put(rk.sd, 4 * nd * nd);
+  }
+  return stage_flush(h, pt.amg_xi, st);
 }
 
 // the distributed V-cycle in its compact form (option amg_dist_cycle)
@@ -2916,6 +2917,7 @@ int ensure_gamg(mfea_handle* h, bool* rebuilt) {
   for (auto& pp : h->parts) {
     Part& pt = *pp;
     if (pt.dev_plan == 1) continue;
+    if (!up) RC(drain_before_upload(h, "plan upload"));
     if (!up) destroy_graph(h);
     up = true;
     RC(upload_amg(h, pt, h->gamg, &pt.amg_rank, &pt.g_a0, &pt.g_row0));
@@ -3484,15 +3486,11 @@ bool ensure_colour(mfea_handle* h, Part& pt) {
   pt.ec_state = -1;
   if (!build_elem_colour(pt.P, pt.ec).empty()) return false;
   if (pt.ec.entry.empty() && pt.P.n_elems) return false;
+  // (two buffers of their own; pt's sources; the assembly that reads them follows on the stream: no wait)
   if (pt.ec_entry.alloc(std::max<size_t>(pt.ec.entry.size(), 1)) != hipSuccess ||
-      pt.ec_pos.alloc(std::max<size_t>(pt.ec.pos.size(), 1)) != hipSuccess)
-    return false;
-  if (!pt.ec.entry.empty() &&
-      hipMemcpyAsync(pt.ec_entry.ptr, pt.ec.entry.data(), pt.ec.entry.size() * sizeof(int32_t),
-                     hipMemcpyHostToDevice, h->stream) != hipSuccess)
-    return false;
-  if (!pt.ec.pos.empty() && hipMemcpyAsync(pt.ec_pos.ptr, pt.ec.pos.data(), pt.ec.pos.size() * sizeof(int32_t),
-                                           hipMemcpyHostToDevice, h->stream) != hipSuccess)
+      pt.ec_pos.alloc(std::max<size_t>(pt.ec.pos.size(), 1)) != hipSuccess ||
+      h2d_async(h, pt.ec_entry.ptr, pt.ec.entry.data(), pt.ec.entry.size() * sizeof(int32_t)) != hipSuccess ||
+      h2d_async(h, pt.ec_pos.ptr, pt.ec.pos.data(), pt.ec.pos.size() * sizeof(int32_t)) != hipSuccess)
     return false;
   pt.ec_state = 1;
   return true;

@@ -629,3 +629,51 @@ def test_setup_entry_in_the_graph_is_bitwise_the_eager_entry(engine, precond):
         runs.append(out)
     for a, b in zip(*runs):
         assert a[0] == b[0] and a[1] == b[1] and np.array_equal(a[2], b[2])
+
+
+@pytest.mark.parametrize("nparts,amg_dist", [(1, -1), (2, 1), (2, 0)])
+def test_plan_rebuild_and_reupload_repeats_bitwise(nparts, amg_dist):
+    """The plan upload (csrc/carve.hpp, capi.hip stage_flush) run again on a
+    handle that already holds a plan's buffers: solve on the intact network,
+    deactivate a handful of elements (amg_reuse 0: the hierarchy is rebuilt
+    and uploaded again), solve, restore the activity, solve.  The first and
+    third solves agree bit for bit; the second matches the direct solve of
+    its K.  (Whether a buffer was kept or grown is not observed here.)  A grown network of 2.5 k nodes (4 k free DOF, planar):
+    small, and still three or more levels, as coarsening runs until no
+    coupling is left.  One partition (the hierarchy and its lists), two with
+    the global hierarchy (the exchange plans) and two with block Jacobi (the
+    halo)."""
+    from mfea import Engine, grow_network, scaled_grow_params, synth
+    xyz, e2n = grow_network(scaled_grow_params(0.6))
+    top, bot = synth.grips(xyz, tol=0.5)  # (every colony then reaches a grip)
+    dy = fo.DISPLACEMENT_MAX * 20 / (fo.N_STEPS - 1)
+    known, vals = fo.known_dof_map(top, bot, dy, -dy)
+    # eight elements spread over the network whose loss cuts no node off the grips
+    active = np.ones(len(e2n), bool)
+    off = []
+    for e in range(7, len(e2n), len(e2n) // 40):
+        active[e] = False
+        if _floating_nodes(xyz, e2n, active, top, bot).any() or len(off) == 8:
+            active[e] = True
+        else:
+            off.append(e)
+    assert len(off) == 8
+    eng = Engine(0)
+    try:
+        eng.set_parts(nparts)
+        with eng.options(amg_reuse=0, amg_dist=amg_dist):
+            eng.set_mesh(xyz, e2n)
+            eng.set_bc(top, bot)
+            runs = []
+            for act in (None, active, None):
+                eng.set_active(act)
+                eng.assemble()
+                st = eng.solve(dy, -dy, _opts(1e-13))
+                assert st.status == 0 and st.amg_levels >= 3 and st.amg_rebuilt == 1
+                runs.append((st.iters, eng.displacement().copy()))
+    finally:
+        eng.close()
+    assert runs[0][0] == runs[2][0] and np.array_equal(runs[0][1], runs[2][1])
+    Uref = fo.solve_system(fo.assemble_global_stiffness(xyz, e2n, active), known, vals)
+    assert rel(runs[1][1], Uref) <= 1e-10, rel(runs[1][1], Uref)
+    assert not np.array_equal(runs[1][1], runs[0][1])
