@@ -210,6 +210,71 @@ int mfea_get_grip_motion(mfea_handle* h, double top[3], double bot[3]);
  * in the tensile test. */
 int mfea_get_reaction(mfea_handle* h, double top[3], double bot[3]);
 
+/* ---- strain energy per element: axial and bending parts, and their gradients - */
+/* The element assembled here has two stiffness terms, k_ax = EA_e/L along the
+ * filament and k_b = EI12_e/L³ across it (EA_e = E_e·A_e, EI12_e = (12·E_e)·I_e).
+ * With δ = u_b − u_a its strain energy ½ δᵀS_eδ is w_axial + w_bending; the
+ * axial stress of mfea_get_stress sees the first part only.  One pass over the
+ * elements, one lane each; every line one IEEE f64 operation per operator, in
+ * this order, nothing fused but inside cube (a = n1, b = n2 of elements.csv):
+ *   v_c  = xyz[b][c] − xyz[a][c]
+ *   L    = sqrt(vx*vx + vy*vy + vz*vz)          the assembly's expression
+ *   Ls   = L < 1e-12 ? 1e-12 : L
+ *   n_c  = v_c / Ls
+ *   δ_c  = U[b][c] − U[a][c]
+ *   d    = (n0*δ0 + n1*δ1) + n2*δ2              axial stretch
+ *   t_c  = δ_c − d*n_c                          transverse part
+ *   q    = (t0*t0 + t1*t1) + t2*t2
+ *   g_axial   = ((0.5*d)*d) / Ls                energy per unit EA_e
+ *   g_bending = (0.5*q) / cube(Ls)              energy per unit EI12_e; cube: the
+ *                                               assembly's double-double Ls³
+ *   w_axial   = EA_e * g_axial      w_bending = EI12_e * g_bending
+ * so w = section · g holds exactly, in bits.  An element that does not count
+ * (inactive in the mask used, or an endpoint dropped under
+ * MFEA_MESH_SKIP_INVALID) gives four zeros.  A zero-length element has n = 0,
+ * d = 0, t = δ and w_bending = ½ k_b |δ|², what K holds for it: the result is
+ * finite wherever K is (no NaN, unlike that element's strain).
+ *   U       3·n_nodes in original node order, or NULL: the handle's current
+ *           displacement, what mfea_get_displacement returns;
+ *   active  n_elems bytes (nonzero = counts), or NULL: the handle's current
+ *           activity.  After a step whose post failed elements, the elements in
+ *           that step's K are those of the activity BEFORE it: a caller who
+ *           wants the step's equilibrium energy passes that mask;
+ *   total   (Σ w_axial, Σ w_bending) over the elements, summed in a fixed order
+ *           (bitwise reproducible for a mesh), or NULL;
+ *   out     the rows wanted, each n_elems doubles in original element order or
+ *           NULL; out itself may be NULL.
+ * Gradients.  W = ½ UᵀKU = Σ_e (w_axial + w_bending).  With the grips'
+ * displacements prescribed, equilibrium of the free rows makes the implicit
+ * term vanish, ∂W/∂θ_e = ½ u_eᵀ(∂K_e/∂θ_e)u_e, so without an adjoint solve
+ *   ∂W/∂E_e = A_e·g_axial + (12·I_e)·g_bending
+ *   ∂W/∂A_e = E_e·g_axial
+ *   ∂W/∂I_e = (12·E_e)·g_bending
+ * These are gradients of the equilibrium energy only when U solves the K of
+ * `active`; for any other U they are the partial derivatives at fixed U.  When
+ * both grips move along the same vector, F = 2W/(dy_top − dy_bot), and the same
+ * rows give the gradient of the reported force.
+ * Work identity, for any U (S: the sums of mfea_get_reaction, top / bot: the
+ * grip directions, f: the free DOFs):
+ *   2W = dy_top·(top·S_top) + dy_bot·(bot·S_bot) + u_fᵀ(KU)_f
+ * the last term being the solver's residual, zero at equilibrium.
+ * Needs a mesh and boundary conditions, not an assembly (MFEA_ESTATE without
+ * them); one partition only (MFEA_ESTATE on a partitioned handle, as
+ * mfea_get_reaction).  The call changes nothing a later call can see: no
+ * generation moves, nothing option "keep_operator" keeps is dropped (the next
+ * step on an unchanged active set is still a kept step), and it is ordered on
+ * the handle's stream behind everything enqueued before it, a speculative
+ * post's undo included.  A caller's U is permuted to row order on the host and
+ * goes into a device buffer allocated at first use. */
+typedef struct {
+  double* w_axial;   /* n_elems or NULL */
+  double* w_bending; /* n_elems or NULL */
+  double* g_axial;   /* n_elems or NULL: w_axial per unit EA_e    */
+  double* g_bending; /* n_elems or NULL: w_bending per unit EI12_e */
+} mfea_element_energy;
+int mfea_get_energy(mfea_handle* h, const double* U, const uint8_t* active, double total[2],
+                    const mfea_element_energy* out);
+
 /* ---- mesh + boundary conditions (symbolic, once per mesh) ------------------ */
 /* Replaces the CSV→array hand-off of fea_solver (src/fea_solver.py:193-201) and
  * read_nodes_csv/read_elems_csv (src/fea_petsc.cpp:42-82, 179-200).

@@ -120,6 +120,13 @@ struct Part {
   const int32_t* amg_inv_row0 = nullptr;
   DevBuf<unsigned> fail_cnt;
   DevBuf<unsigned> tickets;
+  // mfea_get_energy, allocated at its first use on this build: a caller's U in
+  // row order, a caller's mask, the rows asked for (up to four of E doubles)
+  // with the two totals behind them, and the reduction's own partials and
+  // ticket set (no captured graph and no enqueued post holds either)
+  DevBuf<double> en_u, en_out, en_part;
+  DevBuf<uint8_t> en_act;
+  DevBuf<unsigned> en_tix;
   // wave-local lane operator (ell.hip); ell_ok = false → SELL kernel
   Ell L;
   bool ell_ok = false;
@@ -4072,6 +4079,79 @@ int mfea_get_reaction(mfea_handle* h, double top[3], double bot[3]) {
                      nullptr);
     HIPC(hipGetLastError());
     HIPC(hmemcpy(h, out[b], pt.red.ptr + 9 + 3 * b, 3 * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  return 0;
+}
+
+// The strain energy of every element that counts and its two parts per unit
+// section (kernels.hip k_energy), on the handle's stream: behind everything
+// earlier calls enqueued there — a speculative post's undo included — so the
+// displacement and the activity it reads are the ones the getters return.  It
+// writes buffers of its own only: no generation moves, nothing kept is dropped.
+int mfea_get_energy(mfea_handle* h, const double* U, const uint8_t* active, double total[2],
+                    const mfea_element_energy* out) {
+  if (!h) return fail(MFEA_EINVAL, "NULL handle");
+  if (!h->has_mesh) return fail(MFEA_ESTATE, "no mesh: call mfea_set_mesh first");
+  if (h->world > 1 || h->nparts > 1 || h->parts.size() > 1)
+    return fail(MFEA_ESTATE, "mfea_get_energy: one partition per handle");
+  if (h->top.empty() && h->bot.empty())
+    return fail(MFEA_ESTATE, "mfea_get_energy: no boundary conditions (mfea_set_bc)");
+  RC(set_device(h));
+  RC(ensure_built(h));
+  Part& pt = part0(h);
+  const Pattern& P = pt.P;
+  const int64_t N = P.n_nodes, E = P.n_elems;
+  hipStream_t s = h->stream;
+  double* const host[4] = {out ? out->w_axial : nullptr, out ? out->w_bending : nullptr,
+                           out ? out->g_axial : nullptr, out ? out->g_bending : nullptr};
+  int rows = 0;
+  for (double* p : host) rows += p != nullptr;
+  HIPC(pt.en_out.alloc((size_t)rows * E + 2));
+  HIPC(pt.en_part.alloc((size_t)energy_partials(E)));
+  if (U) HIPC(pt.en_u.alloc(3 * N));
+  if (active) HIPC(pt.en_act.alloc(E));
+  const bool first = !pt.en_tix.ptr;
+  HIPC(pt.en_tix.alloc(kTicketStride));
+  // a caller's U, original node order → row order, and a caller's mask; the
+  // host sources live until the stream is waited for below, error or not
+  // (hmemcpy's rule)
+  std::vector<double> up;
+  std::vector<uint8_t> am;
+  if (U) {
+    up.resize(3 * N);
+    for (int64_t i = 0; i < N; ++i)
+      for (int a = 0; a < 3; ++a) up[3 * i + a] = U[3 * P.perm[i] + a];
+  }
+  if (active) {
+    am.resize(E);
+    for (int64_t e = 0; e < E; ++e) am[e] = active[e] ? 1 : 0;
+  }
+  double* dev[4] = {nullptr, nullptr, nullptr, nullptr};
+  double* next = pt.en_out.ptr;
+  for (int k = 0; k < 4; ++k) {
+    if (!host[k]) continue;
+    dev[k] = next;
+    next += E;
+  }
+  double* red = pt.en_out.ptr + (size_t)rows * E;
+  double tot[2] = {0.0, 0.0};
+  hipError_t e = first ? hipMemsetAsync(pt.en_tix.ptr, 0, kTicketStride * sizeof(unsigned), s) : hipSuccess;
+  if (e == hipSuccess && U) e = h2d_async(h, pt.en_u.ptr, up.data(), up.size() * sizeof(double));
+  if (e == hipSuccess && active) e = h2d_async(h, pt.en_act.ptr, am.data(), am.size());
+  if (e == hipSuccess) {
+    launch_energy(s, E, pt.e2n_d.ptr, pt.xyz_d.ptr, U ? pt.en_u.ptr : pt.x.ptr, active ? pt.en_act.ptr : pt.active.ptr,
+                  h->mat, h->sec_d(), EnergyOut{dev[0], dev[1], dev[2], dev[3]}, pt.en_part.ptr, pt.en_tix.ptr, red);
+    e = hipGetLastError();
+  }
+  for (int k = 0; k < 4 && e == hipSuccess; ++k)
+    if (host[k] && E) e = hipMemcpyAsync(host[k], dev[k], E * sizeof(double), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(tot, red, sizeof tot, hipMemcpyDeviceToHost, s);
+  const hipError_t es = hipStreamSynchronize(s);
+  if (e != hipSuccess || es != hipSuccess)
+    return fail(MFEA_EDEVICE, std::string("mfea_get_energy: ") + hipGetErrorString(e != hipSuccess ? e : es));
+  if (total) {
+    total[0] = tot[0];
+    total[1] = tot[1];
   }
   return 0;
 }

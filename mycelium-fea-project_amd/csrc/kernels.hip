@@ -7,6 +7,7 @@
 // fma() where fusion is wanted.
 #include "kernels.hpp"
 #include "device_util.hpp"
+#include "energy.hpp"
 
 #include <math.h>
 
@@ -29,16 +30,9 @@ int64_t grid_elementwise(int64_t n) {
 // src/fea_solver.py:30-68 / src/fea_petsc.cpp:88-140, same rounding sequence as
 // the NumPy reference: L = √((vx²+vy²)+vz²), L_safe = max(L,1e-12), n = v/L_safe,
 // k_ax = EA/L_safe, k_b = EI12/L_safe³, S_ab = (n_a n_b)·k_ax + (δ_ab − n_a n_b)·k_b.
-// L_safe³ is formed in double-double (≈0.5 ulp; NumPy's pow is ≤1 ulp).
+// L_safe³ is formed in double-double (≈0.5 ulp; NumPy's pow is ≤1 ulp): cube,
+// cube.hpp — shared with the element energy (energy.hpp).
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ double cube(double a) {
-  const double s = a * a;
-  const double es = fma(a, a, -s);
-  const double c = s * a;
-  const double ec = fma(s, a, -c);
-  return c + (ec + es * a);
-}
-
 // the section (EA, EI12) of element e: the handle's, or the element's own pair
 __device__ __forceinline__ double2 section_of(const Material& m, int64_t) { return make_double2(m.EA, m.EI12); }
 __device__ __forceinline__ double2 section_of(const ElemSection& m, int64_t e) { return m.sec[e]; }
@@ -706,6 +700,48 @@ __global__ __launch_bounds__(kBlock) void k_unfail(const int32_t* __restrict__ f
 }
 
 // ---------------------------------------------------------------------------
+// Strain energy per element (mfea_get_energy; energy.hpp holds the arithmetic
+// and its operation order): one lane per element, w_ax / w_b / g_ax / g_b of
+// an element that counts — active in the mask given, both endpoints kept —
+// and four zeros otherwise.  Each output array is written only where it was
+// asked for (a uniform branch on a kernel argument).  Reduces (Σ w_ax, Σ w_b)
+// through block_publish: block order, then shard order — the same bits on
+// every call.  Nothing is written but the outputs.
+// Loads: the endpoints, the activity byte and (M = ElemSection) the section
+// pair are indexed by e and issued together; the twelve gathers they lead to
+// (coordinates and displacements of both nodes) are all issued before the
+// first use, as k_stress issues its own — two dependent round trips a lane.
+// ---------------------------------------------------------------------------
+template <class M>
+__global__ __launch_bounds__(kBlock) void k_energy(int64_t E, const int32_t* __restrict__ e2n,
+                                                   const double* __restrict__ xyz,
+                                                   const double* __restrict__ u,
+                                                   const uint8_t* __restrict__ active, M m, EnergyOut out,
+                                                   double* partials, unsigned* ticket, double* red_out) {
+  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  double acc[2] = {0.0, 0.0};
+  if (e < E) {
+    const int32_t a = e2n[2 * e], b = e2n[2 * e + 1];
+    const uint8_t act = active[e];
+    const double2 se = section_of(m, e);
+    ElemEnergy r{0.0, 0.0, 0.0, 0.0};
+    if (act && a >= 0 && b >= 0) {
+      const int64_t ia = 3 * (int64_t)a, ib = 3 * (int64_t)b;
+      const double pa[3] = {xyz[ia], xyz[ia + 1], xyz[ia + 2]}, pb[3] = {xyz[ib], xyz[ib + 1], xyz[ib + 2]};
+      const double ua[3] = {u[ia], u[ia + 1], u[ia + 2]}, ub[3] = {u[ib], u[ib + 1], u[ib + 2]};
+      r = element_energy(pa, pb, ua, ub, se.x, se.y);
+    }
+    if (out.w_axial) out.w_axial[e] = r.w_ax;
+    if (out.w_bending) out.w_bending[e] = r.w_b;
+    if (out.g_axial) out.g_axial[e] = r.g_ax;
+    if (out.g_bending) out.g_bending[e] = r.g_b;
+    acc[0] = r.w_ax;
+    acc[1] = r.w_b;
+  }
+  block_publish<2>(acc, partials, ticket, red_out);
+}
+
+// ---------------------------------------------------------------------------
 // Floating free rows on the device: connected components of the active
 // element graph, then per component whether a grip row is in it.  A free
 // row of a component without a grip is floating: zero load, so the direct
@@ -1074,6 +1110,19 @@ void launch_stress(hipStream_t s, int64_t E, const int32_t* e2n, const double* x
   else
     hipLaunchKernelGGL(k_stress<Material>, MFEA_GRID(grid_rows(E > 0 ? E : 1)), E, e2n, xyz, u, m, max_strain,
                        active, stress, partials, ticket, red_out, owned, fail_list, fail_cnt);
+}
+
+int64_t energy_partials(int64_t n_elems) { return 2 * (grid_rows(n_elems > 0 ? n_elems : 1) + kShards); }
+
+void launch_energy(hipStream_t s, int64_t E, const int32_t* e2n, const double* xyz, const double* u,
+                   const uint8_t* active, Material m, const double2* sec, const EnergyOut& out, double* partials,
+                   unsigned* ticket, double* red_out) {
+  if (sec)
+    hipLaunchKernelGGL(k_energy<ElemSection>, MFEA_GRID(grid_rows(E > 0 ? E : 1)), E, e2n, xyz, u, active,
+                       ElemSection{sec}, out, partials, ticket, red_out);
+  else
+    hipLaunchKernelGGL(k_energy<Material>, MFEA_GRID(grid_rows(E > 0 ? E : 1)), E, e2n, xyz, u, active, m, out,
+                       partials, ticket, red_out);
 }
 
 void launch_unfail(hipStream_t s, const int32_t* fail_list, unsigned* cnt, uint8_t* active) {

@@ -198,6 +198,21 @@ void launch_stress(hipStream_t s, int64_t E, const int32_t* e2n, const double* x
                    const uint8_t* owned = nullptr, int32_t* fail_list = nullptr, unsigned* fail_cnt = nullptr,
                    const double* Ee = nullptr, const double* strength = nullptr);
 
+// k_energy (mfea_get_energy): per element the axial and transverse strain
+// energy and the two per unit section (energy.hpp), E doubles per non-null
+// array; red_out[0..1] = (Σ w_axial, Σ w_bending) in block_publish's fixed
+// order.  active: the mask that says which elements count.  sec (non-null):
+// the per-element (EA_e, EI12_e) pairs instead of m's.  partials:
+// energy_partials(E) doubles; they and the ticket set are the call's own — no
+// captured graph and no enqueued post holds them.
+int64_t energy_partials(int64_t n_elems);
+struct EnergyOut {
+  double *w_axial, *w_bending, *g_axial, *g_bending;
+};
+void launch_energy(hipStream_t s, int64_t E, const int32_t* e2n, const double* xyz, const double* u,
+                   const uint8_t* active, Material m, const double2* sec, const EnergyOut& out, double* partials,
+                   unsigned* ticket, double* red_out);
+
 // ---- event-driven failure runs (events.hip) ---------------------------------
 // k_event_scan: the reaction of the top grip rows (launch_reaction's arguments;
 // force_out gets k_reaction's bits) and, in the same launch, the elements'

@@ -239,7 +239,8 @@ TENSILE = (0.0, 1.0, 0.0)
 
 def fea_solver(results_dir, tol=GRIP_LENGTH, *, rtol=None, max_it=None, precond=None,
                out_format="python", verbose=True, nparts=1, npy=False, device_run=False,
-               events=False, tie_rtol=1e-9, max_events=None, element_props=None, grip_direction=None):
+               events=False, tie_rtol=1e-9, max_events=None, element_props=None, grip_direction=None,
+               energy=False):
     """The reference step loop (src/fea_solver.py:186-335) with the hot path on device.
 
     Reads <results_dir>/nodes.csv + elements.csv, runs N_STEPS load steps and
@@ -284,9 +285,23 @@ def fea_solver(results_dir, tol=GRIP_LENGTH, *, rtol=None, max_it=None, precond=
     along them (Engine.set_grip_motion), dy_top / dy_bot being the amplitudes:
     a shear or mixed-mode test.  None: the tensile test along y.  Works with the
     ramp, device_run, events and element_props; force_displacement.csv keeps its
-    two columns, the amplitude span and the work-conjugate force."""
+    two columns, the amplitude span and the work-conjugate force.
+
+    energy=True (one process, one partition): the strain energy of every record
+    row, split into its axial and bending parts (Engine.energy /
+    mfea_get_energy), each row on the activity its K was assembled from — the
+    one BEFORE the step's or event's failures.  The per-step path asks after
+    every step; device_run and events ask once per recorded row afterwards,
+    with U row k and activity row k − 1 (an event's U row is lam_k·U₁, so its
+    energy is that at the failure load).  Writes energy.csv (step,
+    total_displacement, axial_energy, bending_energy) and
+    element_energy_axial.csv / element_energy_bending.csv in the stress
+    record's layout and out_format (.npy sidecars with npy); the returned dict
+    gains "energy" (rows × 2), "w_axial" and "w_bending"."""
     start_time = time.time()
     rank, world = dist_env()
+    if energy and (world > 1 or nparts > 1):
+        raise ValueError("energy needs one process and one partition (world == 1, nparts == 1)")
     if grip_direction is not None and (world > 1 or nparts > 1):
         raise ValueError("grip_direction needs one process and one partition (world == 1, nparts == 1)")
     if isinstance(grip_direction, str):
@@ -334,6 +349,8 @@ def fea_solver(results_dir, tol=GRIP_LENGTH, *, rtol=None, max_it=None, precond=
     node_owned, elem_owned = eng.ownership() if world > 1 else (None, None)
 
     stress_record, active_record, disp_record, force_disp_curve, solve_times = [], [], [], [], []
+    energy_record, wax_record, wb_record = [], [], []
+    act_before = eng.active() if energy else None  # the activity the next K is assembled from
     if rank == 0:
         with open(os.path.join(fea_dir, "solve_runtime.txt"), "w") as f:
             f.write("step, runtime_s\n")
@@ -342,6 +359,10 @@ def fea_solver(results_dir, tol=GRIP_LENGTH, *, rtol=None, max_it=None, precond=
             eng, opts, fea_dir, say, tie_rtol, max_events, npy)
     elif device_run:
         stress_record, active_record, disp_record, force_disp_curve = _device_run(eng, opts, fea_dir, say)
+    if energy and (events or device_run):
+        for k in range(len(disp_record)):
+            _energy_row(eng, disp_record[k], act_before if k == 0 else active_record[k - 1],
+                        energy_record, wax_record, wb_record)
     for step in range(0 if device_run or events else N_STEPS):  # the per-step path
         disp_factor = step / (N_STEPS - 1)
         dy_top = +DISPLACEMENT_MAX * disp_factor
@@ -367,6 +388,9 @@ def fea_solver(results_dir, tol=GRIP_LENGTH, *, rtol=None, max_it=None, precond=
             disp_record.append(rec[0])
             stress_record.append(rec[1])
             active_record.append(rec[2])
+        if energy:  # the handle's U, the activity before this step's failures
+            _energy_row(eng, None, act_before, energy_record, wax_record, wb_record)
+            act_before = rec[2]
         if n_active == 0:
             say(f"⚠️  Simulation stopped early at step {step+1}.")
             break
@@ -374,13 +398,29 @@ def fea_solver(results_dir, tol=GRIP_LENGTH, *, rtol=None, max_it=None, precond=
     if rank == 0:
         write_records(fea_dir, n_nodes, n_elems, stress_record, active_record, disp_record,
                       force_disp_curve, out_format, npy=npy)
+        if energy:
+            write_energy(fea_dir, n_elems, force_disp_curve, energy_record, wax_record, wb_record, out_format,
+                         npy=npy)
         say(f"✅ FEA completed. Results saved to {fea_dir}")
         total_time = time.time() - start_time
         with open(os.path.join(fea_dir, "runtime.txt"), "w") as f:
             f.write(f"Total FEA runtime: {total_time:.6f} seconds\n")
         say(f"⏱️ Total runtime: {total_time:.3f} seconds")
-    return {"force": np.asarray(force_disp_curve), "stress": np.asarray(stress_record),
-            "active": np.asarray(active_record), "U": np.asarray(disp_record)}
+    res = {"force": np.asarray(force_disp_curve), "stress": np.asarray(stress_record),
+           "active": np.asarray(active_record), "U": np.asarray(disp_record)}
+    if energy:
+        res.update(energy=np.asarray(energy_record, dtype=np.float64).reshape(-1, 2),
+                   w_axial=np.asarray(wax_record), w_bending=np.asarray(wb_record))
+    return res
+
+
+def _energy_row(eng, U, active, energy_record, wax_record, wb_record):
+    """One record row of fea_solver(energy=True): the two totals and the two
+    element rows of Engine.energy(U, active), appended to the three lists."""
+    en = eng.energy(U=U, active=active)
+    energy_record.append([en["axial"], en["bending"]])
+    wax_record.append(en["w_axial"])
+    wb_record.append(en["w_bending"])
 
 
 def _device_run(eng, opts, fea_dir, say):
@@ -462,6 +502,26 @@ def write_records(fea_dir, n_nodes, n_elems, stress_record, active_record, disp_
             _capi.write_record_npy(os.path.join(fea_dir, name[:-4] + ".npy"), kind, rec, n_cols=ncol)
 
 
+def write_energy(fea_dir, n_elems, force_disp_curve, energy_record, wax_record, wb_record,
+                 out_format="python", npy=False):
+    """The files of fea_solver(energy=True): energy.csv — one line per record
+    row, floats as Python's repr writes them — and the two element records
+    through the native writer, in the stress record's layout (petsc: written
+    only when they hold a row, as write_records)."""
+    with open(os.path.join(fea_dir, "energy.csv"), "w") as f:
+        f.write("step,total_displacement,axial_energy,bending_energy\n")
+        for k, (w_ax, w_b) in enumerate(energy_record):
+            f.write(f"{k+1},{float(force_disp_curve[k][0])!r},{float(w_ax)!r},{float(w_b)!r}\n")
+    petsc = out_format == "petsc"
+    style = _capi.CSV_PETSC if petsc else _capi.CSV_PANDAS
+    for name, rec in (("element_energy_axial.csv", wax_record), ("element_energy_bending.csv", wb_record)):
+        if petsc and not len(rec):
+            continue
+        _capi.write_record_csv(os.path.join(fea_dir, name), style, _capi.REC_STRESS, rec, n_cols=n_elems)
+        if npy:
+            _capi.write_record_npy(os.path.join(fea_dir, name[:-4] + ".npy"), _capi.REC_STRESS, rec, n_cols=n_elems)
+
+
 def main(argv=None):
     global N_STEPS, DISPLACEMENT_MAX, MAX_STRAIN, REG
     ap = argparse.ArgumentParser(description="MI355X FEA (drop-in for src/fea_solver.py)")
@@ -496,7 +556,13 @@ def main(argv=None):
                          "(bottom: the same as the top's unless given; one process, one partition); "
                          "default 0,1,0: the tensile test")
     ap.add_argument("--shear", action="store_true", help="shorthand for --grip-direction 1,0,0")
+    ap.add_argument("--energy", action="store_true",
+                    help="also write the strain energy of every record row, axial and bending parts: energy.csv, "
+                         "element_energy_axial.csv, element_energy_bending.csv (one process, one partition)")
     a = ap.parse_args(argv)
+    if a.energy and a.parts > 1:
+        print("fea_solver: --energy needs one partition (--parts 1)", file=sys.stderr)
+        sys.exit(2)
     grip = None
     if a.shear and a.grip_direction is not None:
         print("fea_solver: --shear and --grip-direction exclude each other", file=sys.stderr)
@@ -521,7 +587,7 @@ def main(argv=None):
                         "bjacobi": _capi.PC_BLOCK_JACOBI, "sor": _capi.PC_SOR, "icc": _capi.PC_ICC}[a.pc],
                out_format=a.format, nparts=a.parts, npy=a.npy, device_run=a.device_run,
                events=a.events, tie_rtol=a.tie_rtol, max_events=a.max_events, element_props=props,
-               grip_direction=grip)
+               grip_direction=grip, energy=a.energy)
 
 
 if __name__ == "__main__":

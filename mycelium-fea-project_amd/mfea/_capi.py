@@ -71,6 +71,12 @@ class ElementProps(C.Structure):
     _fields_ = [("E", C.c_void_p), ("A", C.c_void_p), ("I", C.c_void_p), ("max_strain", C.c_void_p)]
 
 
+class ElementEnergy(C.Structure):
+    """mfea_element_energy (include/mfea.h): the rows wanted, NULL = not wanted."""
+    _fields_ = [("w_axial", C.c_void_p), ("w_bending", C.c_void_p), ("g_axial", C.c_void_p),
+                ("g_bending", C.c_void_p)]
+
+
 class EventRecords(C.Structure):
     """mfea_event_records (include/mfea.h): where mfea_run_events writes each event's rows."""
     _fields_ = [("U", C.c_void_p), ("stress", C.c_void_p), ("active", C.c_void_p),
@@ -121,6 +127,7 @@ _sig = {
     "mfea_set_grip_motion": (C.c_int, [_P, _P, _P]),
     "mfea_get_grip_motion": (C.c_int, [_P, _P, _P]),
     "mfea_get_reaction": (C.c_int, [_P, _P, _P]),
+    "mfea_get_energy": (C.c_int, [_P, _P, _P, _P, C.POINTER(ElementEnergy)]),
     "mfea_set_mesh": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_uint32]),
     "mfea_set_bc": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P]),
     "mfea_set_active": (C.c_int, [_P, _P]),
@@ -540,6 +547,44 @@ class Engine:
         top, bot = np.empty(3), np.empty(3)
         _check(_lib.mfea_get_reaction(self._h, _ptr(top), _ptr(bot)))
         return top, bot
+
+    ENERGY_ROWS = ("w_axial", "w_bending", "g_axial", "g_bending")
+
+    def energy(self, U=None, active=None, elements=True) -> dict:
+        """Strain energy per element, split into its axial and bending parts
+        (mfea_get_energy).  U: 3 * n_nodes in original node order, None = the
+        handle's current displacement; active: one entry per element saying
+        which count, None = the handle's current activity (after a step that
+        failed elements, that step's K held the activity before it).  Returns
+        {"axial", "bending"}, the two totals, and with elements=True the rows
+        w_axial, w_bending (energies) and g_axial, g_bending (the same per unit
+        EA_e / EI12_e), in original element order."""
+        if U is not None:
+            U = np.ascontiguousarray(U, dtype=np.float64).ravel()
+            if U.size != 3 * self.n_nodes:
+                raise ValueError("U must have three entries per node")
+        if active is not None:
+            active = np.ascontiguousarray(active, dtype=np.uint8).ravel()
+            if active.size != self.n_elems:
+                raise ValueError("active must have one entry per element")
+        total = np.zeros(2)
+        rows = {k: np.empty(self.n_elems) for k in self.ENERGY_ROWS} if elements else {}
+        out = ElementEnergy(*(_ptr(rows[k]) for k in self.ENERGY_ROWS)) if elements else None
+        _check(_lib.mfea_get_energy(self._h, _ptr(U), _ptr(active), _ptr(total),
+                                    C.byref(out) if elements else None))
+        return {"axial": float(total[0]), "bending": float(total[1]), **rows}
+
+    def energy_gradient(self, U=None, active=None) -> dict:
+        """{"E", "A", "I"}: the derivative of the strain energy W = ½ UᵀKU with
+        respect to each element's modulus, area and second moment, from the
+        g rows of energy() and element_props() (include/mfea.h):
+        dW/dE_e = A_e g_ax + (12 I_e) g_b, dW/dA_e = E_e g_ax,
+        dW/dI_e = (12 E_e) g_b.  Gradients of the equilibrium energy when U
+        solves the K of `active`."""
+        en, p = self.energy(U, active), self.element_props()
+        return {"E": p["A"] * en["g_axial"] + (12.0 * p["I"]) * en["g_bending"],
+                "A": p["E"] * en["g_axial"],
+                "I": (12.0 * p["E"]) * en["g_bending"]}
 
     def set_bc(self, top, bot):
         top = np.ascontiguousarray(top, dtype=np.int64).ravel()
