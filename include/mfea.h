@@ -210,6 +210,70 @@ int mfea_get_grip_motion(mfea_handle* h, double top[3], double bot[3]);
  * in the tensile test. */
 int mfea_get_reaction(mfea_handle* h, double top[3], double bot[3]);
 
+/* ---- grip displacement field: a prescribed vector per grip node -------------- */
+/* field: 3·n_nodes doubles, original node order, row n = the vector d_n of node
+ * n; NULL: no field (back to mfea_set_grip_motion's two vectors).  Copied.
+ * Grip rotation d_n = a × (x_n − c), an affine boundary displacement
+ * d_n = H·x_n, an indentation (zero rows: held nodes) are fields.
+ *   value     with a field, a node n in a band is prescribed
+ *             p[c] = fl(a_n·d_n[c]), one f64 product per component, with
+ *             a_n = dy_bot if n is in the bottom band, otherwise dy_top (a node
+ *             in both bands is a bottom node, as in the tensile test).  Rows of
+ *             nodes in no band are stored and otherwise ignored.  While a field
+ *             is set the two vectors of mfea_set_grip_motion are read nowhere;
+ *             they are kept, still settable and gettable, and take over again
+ *             when the field is cleared.
+ *   RHS       mfea_set_grip_motion's rule with p per neighbour: a free row with
+ *             a known neighbour j takes b −= V·p_j, each row of V·p_j one fma
+ *             chain in component order, the neighbours in slot order.  A known
+ *             row gets x = p.
+ *   force     wherever the API returns a force (total_force, mfea_run_records
+ *             .force, force1 of events) it is the generalised force of the top
+ *             band, F = Σ_{top rows} w_r,
+ *               w_r = (d_r[0]·f_r[0] + d_r[1]·f_r[1]) + d_r[2]·f_r[2],
+ *             f_r = (K·U) of row r as mfea_get_reaction accumulates it; f64
+ *             products and sums in this order, nothing fused; the rows reduced
+ *             in a fixed order, bitwise reproducible for a mesh.
+ *             mfea_get_reaction is unchanged: plain component sums.
+ *   events    the prescribed displacement stays amplitude × a fixed vector per
+ *             node, so U ∝ amplitude on a fixed active set: mfea_event's rules
+ *             stand unchanged, force1 as above.
+ * MFEA_ESTATE before mfea_set_mesh.  MFEA_EINVAL, the handle unchanged, unless
+ * every entry is finite.  Zero rows are legal: a held node.  −0 is stored as 0.
+ * Lifetime: mfea_set_mesh clears the field (the node count changes);
+ * mfea_set_bc, mfea_set_active, mfea_set_material, mfea_set_element_props and
+ * mfea_set_grip_motion keep it; it is gathered into row order again at every
+ * build.
+ * One partition only: MFEA_ESTATE on a partitioned handle; a handle with a
+ * field that is partitioned afterwards returns MFEA_ESTATE from its next build.
+ * A change — another field, or NULL — drops exactly what a change of the grip
+ * directions drops: the right-hand side a step cached and every captured graph,
+ * after draining the stream.  K, the symbolic hierarchy and everything option
+ * "keep_operator" keeps stay: the next step is a kept step (amg_rebuilt == 0).
+ * Setting the same bytes again drops nothing.
+ * Planar meshes (every z == 0): with any z entry of the stored field non-zero
+ * the handle solves with 3 DOFs per node, and the change takes the rebuild a
+ * layout option takes (the activity is kept); clearing the field, or setting
+ * one with every z entry zero, goes back to 2.
+ * Uniform identity: a field whose rows equal the band vectors (the top vector
+ * on nodes only in the top band, the bottom vector on bottom-band nodes) gives
+ * U, iteration counts, stress, activity, n_active, lam and n_failed bit for bit
+ * those of mfea_set_grip_motion with these vectors, for every preconditioner;
+ * the force differs by summation order only, Σ d·f against d·Σ f. */
+int mfea_set_grip_field(mfea_handle* h, const double* field);
+/* field (3·n_nodes, may be NULL) as stored; *is_set 0/1 (may be NULL).  Not set:
+ * every row filled with the vector its node's band would use (bottom wins),
+ * rows of nodes in no band with zeros. */
+int mfea_get_grip_field(mfea_handle* h, double* field, int32_t* is_set);
+/* The work-conjugate (generalised) force of each band on the unregularised K of
+ * the last assembly and the current U; either may be NULL.  States as
+ * mfea_get_reaction.  With a field: G = Σ_{band rows} w_r as above; the top
+ * value has the bits of the total_force a post of this U returns.  Without:
+ *   G = (v[0]·S[0] + v[1]·S[1]) + v[2]·S[2]
+ * with v the band's direction and S its sums of mfea_get_reaction; for the top
+ * band those are total_force's bits. */
+int mfea_get_grip_work(mfea_handle* h, double* top, double* bot);
+
 /* ---- strain energy per element: axial and bending parts, and their gradients - */
 /* The element assembled here has two stiffness terms, k_ax = EA_e/L along the
  * filament and k_b = EI12_e/L³ across it (EA_e = E_e·A_e, EI12_e = (12·E_e)·I_e).
@@ -257,7 +321,9 @@ int mfea_get_reaction(mfea_handle* h, double top[3], double bot[3]);
  * Work identity, for any U (S: the sums of mfea_get_reaction, top / bot: the
  * grip directions, f: the free DOFs):
  *   2W = dy_top·(top·S_top) + dy_bot·(bot·S_bot) + u_fᵀ(KU)_f
- * the last term being the solver's residual, zero at equilibrium.
+ * the last term being the solver's residual, zero at equilibrium.  In general,
+ * grip field or not, with G the two values of mfea_get_grip_work:
+ *   2W = dy_top·G_top + dy_bot·G_bot + u_fᵀ(KU)_f
  * Needs a mesh and boundary conditions, not an assembly (MFEA_ESTATE without
  * them); one partition only (MFEA_ESTATE on a partitioned handle, as
  * mfea_get_reaction).  The call changes nothing a later call can see: no

@@ -1406,7 +1406,7 @@ __global__ __launch_bounds__(kBlock) void k_amg_row0_inverse(AmgCg cg, int32_t* 
 // vcycle_entry: level 0's D⁻¹ and ω must be current, i.e. the setup kept),
 // and the reduction's last block k_cg_init_finalize's: the state, and the
 // zeroing of the partial buffers.
-// GM: GripY, or GripVec — k_amg_rhs<GripVec>'s row body (kernels.hpp).
+// GM: GripY, or GripVec / GripField — k_amg_rhs<GM>'s row body (kernels.hpp).
 template <int ND, class GM>
 __global__ __launch_bounds__(kBlock) void k_amg_start(SellOp op, const uint8_t* __restrict__ code, double dy_top,
                                                       double dy_bot, CgVecs v, double* partials, unsigned* ticket,
@@ -1421,7 +1421,8 @@ __global__ __launch_bounds__(kBlock) void k_amg_start(SellOp op, const uint8_t* 
   if constexpr (VEC) gp = grip_disp(g, dy_top, dy_bot);
   if (row < op.nf) {
     double b[3];
-    amg_rhs_row<GM>(op, code, dy_top, dy_bot, row, b, &gp);
+    if constexpr (std::is_same<GM, GripField>::value) amg_rhs_row<GM>(op, code, dy_top, dy_bot, row, b, nullptr, g.d);
+    else amg_rhs_row<GM>(op, code, dy_top, dy_bot, row, b, &gp);
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       v.r[0][3 * row + a] = b[a];
@@ -1446,6 +1447,11 @@ __global__ __launch_bounds__(kBlock) void k_amg_start(SellOp op, const uint8_t* 
     if constexpr (VEC) {
       double xk[3];
       grip_of(gp, c, xk);
+#pragma unroll
+      for (int a = 0; a < 3; ++a) v.x[3 * row + a] = xk[a];
+    } else if constexpr (std::is_same<GM, GripField>::value) {
+      double xk[3];
+      grip_of(g, row, op.nf, c, dy_top, dy_bot, xk);
 #pragma unroll
       for (int a = 0; a < 3; ++a) v.x[3 * row + a] = xk[a];
     } else {
@@ -2324,9 +2330,18 @@ void launch_amg_row0_inverse(hipStream_t s, const AmgCg& cg, int32_t* inv, int64
 void launch_amg_start(hipStream_t s, int nd, const SellOp& op, const uint8_t* code, double dy_top, double dy_bot,
                       const CgVecs& v, double* partials, unsigned* ticket, double* red_out, const AmgLevD& L0,
                       const AmgCg& cg, const int32_t* inv, double rtol, double atol, int norm, int max_it,
-                      double reg, SolveState* st, double* zero, int64_t nzero, const GripVec* grip) {
+                      double reg, SolveState* st, double* zero, int64_t nzero, const GripVec* grip,
+                      const double* field) {
   const dim3 grid((unsigned)grid_rows(op.N > 0 ? op.N : 1));  // k_amg_rhs's (launch_cg_rhs)
-  if (grip && nd == 2)
+  if (field && nd == 2)
+    hipLaunchKernelGGL((k_amg_start<2, GripField>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials,
+                       ticket, red_out, L0, cg, inv, rtol, atol, norm, max_it, reg, st, zero, nzero,
+                       GripField{field});
+  else if (field)
+    hipLaunchKernelGGL((k_amg_start<3, GripField>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials,
+                       ticket, red_out, L0, cg, inv, rtol, atol, norm, max_it, reg, st, zero, nzero,
+                       GripField{field});
+  else if (grip && nd == 2)
     hipLaunchKernelGGL((k_amg_start<2, GripVec>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials,
                        ticket, red_out, L0, cg, inv, rtol, atol, norm, max_it, reg, st, zero, nzero, *grip);
   else if (grip)

@@ -127,6 +127,10 @@ struct Part {
   DevBuf<double> en_u, en_out, en_part;
   DevBuf<uint8_t> en_act;
   DevBuf<unsigned> en_tix;
+  // mfea_set_grip_field: the field's vectors of the known rows in row order
+  // (kernels.hpp GripField; at least 3 doubles), uploaded by the setter and at
+  // each build; mfea_get_grip_work's outputs (sums[0..2] of a band, the value)
+  DevBuf<double> grip_d, gw_red;
   // wave-local lane operator (ell.hip); ell_ok = false → SELL kernel
   Ell L;
   bool ell_ok = false;
@@ -295,7 +299,17 @@ struct mfea_handle : Options {
            grip.bot[1] == 1.0 && grip.bot[2] == 0.0;
   }
   const GripVec* grip_arg() const { return grip_default() ? nullptr : &grip; }
-  bool grip_z() const { return grip.top[2] != 0.0 || grip.bot[2] != 0.0; }
+  // mfea_set_grip_field (one partition): a vector per node, original node
+  // order, host copy.  While set it takes the place of the two directions
+  // everywhere (they are kept, and read nowhere): the GripField kernels.
+  std::vector<double> field;
+  bool has_field = false;
+  bool grip_z() const {
+    if (!has_field) return grip.top[2] != 0.0 || grip.bot[2] != 0.0;
+    for (size_t n = 2; n < field.size(); n += 3)
+      if (field[n] != 0.0) return true;
+    return false;
+  }
   // host-side mesh/BC (original order)
   int64_t N = 0, Ecount = 0;
   std::vector<double> xyz;
@@ -586,6 +600,22 @@ int upload_props(mfea_handle* h) {
   return 0;
 }
 
+// The grip field's vectors of the known rows, gathered into Pattern row order
+// (row j at 3·(j − n_free)) and uploaded; waited for, before and after.
+int upload_field(mfea_handle* h, Part& pt) {
+  const Pattern& P = pt.P;
+  const int64_t nk = P.n_nodes - P.n_free;
+  std::vector<double> rows((size_t)3 * std::max<int64_t>(nk, 1), 0.0);
+  for (int64_t r = 0; r < nk; ++r)
+    for (int c = 0; c < 3; ++c) rows[3 * r + c] = h->field[3 * (size_t)P.perm[P.n_free + r] + c];
+  HIPC(hipStreamSynchronize(h->stream));
+  HIPC(pt.grip_d.alloc(rows.size()));
+  HIPC(hmemcpy(h, pt.grip_d.ptr, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice));
+  return 0;
+}
+// the kernels' `field` argument: null without a grip field
+const double* field_arg(const mfea_handle* h, const Part& pt) { return h->has_field ? pt.grip_d.ptr : nullptr; }
+
 double* cg_part_buf(Part& pt, int par) { return pt.cg_part.ptr + (size_t)par * 4 * kCgMaxPartials; }
 
 void destroy_graph(mfea_handle* h) {
@@ -624,6 +654,7 @@ int order_mode(const mfea_handle* h) { return h->opt_order; }
 // planar meshes run with 2 DOFs per node (option "lane_dof" 3 forces 3, and
 // so does a grip motion with a z component: the solution leaves the plane);
 // decided on the whole mesh so every partition exchanges records of one width
+// (grip_z: of the field's rows while a grip field is set)
 int lane_dofs(const mfea_handle* h) { return (h->planar && h->opt_lane_dof != 3 && !h->grip_z()) ? 2 : 3; }
 
 // Waits for an event.  Partitioned over RCCL: polls with a deadline and the
@@ -823,6 +854,8 @@ int ensure_built(mfea_handle* h) {
   const bool dm = h->world > 1 || h->nparts > 1;
   if (dm && h->has_props())
     return fail(MFEA_ESTATE, "per-element properties: one partition per handle (mfea_set_element_props(h, NULL) first)");
+  if (dm && h->has_field)
+    return fail(MFEA_ESTATE, "grip field: one partition per handle (mfea_set_grip_field(h, NULL) first)");
   if (dm && !h->grip_default())
     return fail(MFEA_ESTATE, "grip motion: one partition per handle (set the directions (0,1,0), (0,1,0) first)");
   const int np = h->world > 1 ? 1 : h->nparts;
@@ -855,6 +888,7 @@ int ensure_built(mfea_handle* h) {
       pt.mirror = pt.state_mirror.ptr;
     }
     RC(upload_part(h, pt, dm));
+    if (h->has_field) RC(upload_field(h, pt));
   }
   if (dm) {  // distributed GAMG: the whole mesh's pattern and the node owners
     h->gamg_ok = false;
@@ -1357,7 +1391,7 @@ int solve_impl(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_op
   const CgVecs v = cg_vecs(pt);
   RC(phase_event(h, h->ev[1], s));
   launch_cg_rhs(s, op, pt.code.ptr, dy_top, dy_bot, o->reg, precond, v, pt.partials.ptr, tix(pt, 0),
-                pt.red.ptr, h->grip_arg());
+                pt.red.ptr, h->grip_arg(), field_arg(h, pt));
   launch_cg_init_finalize(s, pt.red.ptr, o->rtol, o->atol, o->norm, o->max_it, o->reg,
                           pt.state.ptr,
                           pt.cg_part.ptr, 2 * 4 * kCgMaxPartials);
@@ -2363,6 +2397,7 @@ void enqueue_step_head(mfea_handle* h, Part& pt, const mfea_solve_opts* o) {
   q.dyp = h->d_dy.ptr;
   q.grip = h->grip;
   q.vec = !h->grip_default();
+  q.field = field_arg(h, pt);
   q.nf = P.n_free;
   q.r = pt.r.ptr;
   q.x = pt.x.ptr;
@@ -2570,12 +2605,13 @@ int solve_amg(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opt
       }
       launch_amg_start(s, nd, op, pt.code.ptr, dy_top, dy_bot, v, pt.partials.ptr, tix(pt, 0), pt.red.ptr,
                        pt.amg_lev[0], pt.amg_cg, pt.amg_inv.ptr, o->rtol, o->atol, o->norm, o->max_it, o->reg,
-                       pt.state.ptr, pt.cg_part.ptr, 2 * 4 * kCgMaxPartials, h->grip_arg());
+                       pt.state.ptr, pt.cg_part.ptr, 2 * 4 * kCgMaxPartials, h->grip_arg(),
+                       field_arg(h, pt));
       ++h->amg_start_fused;
     } else {
       if (!rhs_done)
         launch_cg_rhs(s, op, pt.code.ptr, dy_top, dy_bot, o->reg, 2, v, pt.partials.ptr, tix(pt, 0), pt.red.ptr,
-                      h->grip_arg());
+                      h->grip_arg(), field_arg(h, pt));
       if (!start_in_graph)
         launch_cg_init_finalize(s, pt.red.ptr, o->rtol, o->atol, o->norm, o->max_it, o->reg, pt.state.ptr,
                                 pt.cg_part.ptr, 2 * 4 * kCgMaxPartials);
@@ -3532,6 +3568,7 @@ int assemble_impl(mfea_handle* h, mfea_stats* st, const double* rhs_dy = nullptr
       q.dy_bot = rhs_dy[1];
       q.grip = h->grip;
       q.vec = !h->grip_default();
+      q.field = field_arg(h, pt);
       q.nf = P.n_free;
       q.r = pt.r.ptr;
       q.x = pt.x.ptr;
@@ -3651,7 +3688,12 @@ int enqueue_post_work(mfea_handle* h, double max_strain) {
     const Pattern& P = pt.P;
     // (other directions than the tensile test's: the reaction vector of the
     // top rows into red[9..11] and the work-conjugate force into red[4], one launch)
-    if (h->grip_arg())
+    // (a grip field: the generalised force Σ d·f of the top rows into red[4])
+    if (h->has_field)
+      launch_reaction_field(s, P.n_free, P.n_top, P.n_nodes, pt.slice_ptr.ptr, pt.row_len.ptr, pt.s_col.ptr,
+                            pt.val.ptr, pt.diag.ptr, pt.G, pt.x.ptr, pt.partials.ptr, tix(pt, 3), pt.red.ptr + 4,
+                            pt.grip_d.ptr);
+    else if (h->grip_arg())
       launch_reaction3(s, P.n_free, P.n_top, P.n_nodes, pt.slice_ptr.ptr, pt.row_len.ptr, pt.s_col.ptr, pt.val.ptr,
                        pt.diag.ptr, pt.G, pt.x.ptr, pt.partials.ptr, tix(pt, 3), pt.red.ptr + 9, h->grip.top,
                        pt.red.ptr + 4);
@@ -3689,7 +3731,7 @@ int enqueue_event_work(mfea_handle* h) {
   hipStream_t s = h->stream;
   Part& pt = part0(h);
   const Pattern& P = pt.P;
-  const bool vec = !h->grip_default();
+  const bool vec = !h->grip_default() && !h->has_field;
   if ((int64_t)pt.partials.n < event_scan_partials(P.n_top, P.n_elems, vec))
     return fail(MFEA_EINVAL, "internal: partials too small for the event scan");
   double* eps = h->opt_event_scratch ? pt.eps.ptr : nullptr;
@@ -3719,6 +3761,7 @@ int enqueue_event_work(mfea_handle* h) {
   q.vec = vec;
   for (int c = 0; c < 3; ++c) q.w[c] = h->grip.top[c];
   q.sums = pt.red.ptr + 9;
+  q.field = field_arg(h, pt);  // (the top rows are the first known rows)
   launch_event_scan(s, q);
   EventApply a{};
   a.E = P.n_elems;
@@ -4008,6 +4051,26 @@ int mfea_set_material(mfea_handle* h, double E, double A, double I) {
 // kernels' GripY / GripVec form by value) — the stream is drained first, so
 // none is in flight.  A z component on a planar mesh changes the lane layout
 // (lane_dofs): the rebuild a layout option takes, the activity kept.
+// (nd0: lane_dofs before the change)
+static int grip_changed(mfea_handle* h, int nd0) {
+  h->rhs_fused = false;
+  destroy_graph(h);
+  for (auto& gs : h->graph_setup) {
+    if (gs) (void)hipGraphExecDestroy(gs);
+    gs = nullptr;
+  }
+  for (auto& form : h->graph_combo)
+    for (auto& gc : form) {
+      if (gc) (void)hipGraphExecDestroy(gc);
+      gc = nullptr;
+    }
+  if (lane_dofs(h) != nd0) {
+    if (!h->dirty && h->has_mesh && h->Ecount) RC(gather_active(h, h->active_host));
+    h->dirty = true;
+  }
+  return 0;
+}
+
 int mfea_set_grip_motion(mfea_handle* h, const double top[3], const double bot[3]) {
   if (!h) return fail(MFEA_EINVAL, "NULL handle");
   // (what the next build will be decides, not the partitions a handle still
@@ -4031,21 +4094,53 @@ int mfea_set_grip_motion(mfea_handle* h, const double top[3], const double bot[3
   const int nd0 = lane_dofs(h);
   if (h->stream) HIPC(hipStreamSynchronize(h->stream));
   h->grip = g;
-  h->rhs_fused = false;
-  destroy_graph(h);
-  for (auto& gs : h->graph_setup) {
-    if (gs) (void)hipGraphExecDestroy(gs);
-    gs = nullptr;
-  }
-  for (auto& form : h->graph_combo)
-    for (auto& gc : form) {
-      if (gc) (void)hipGraphExecDestroy(gc);
-      gc = nullptr;
+  return grip_changed(h, nd0);
+}
+
+// A vector per grip node in place of the band's direction: it enters where the
+// directions enter and a change drops what a change of them drops
+// (grip_changed).  The host copy is the state; the device rows are gathered
+// from it here, when the handle is built, and at every build.
+int mfea_set_grip_field(mfea_handle* h, const double* field) {
+  if (!h) return fail(MFEA_EINVAL, "NULL handle");
+  if (!h->has_mesh) return fail(MFEA_ESTATE, "set the mesh before the grip field");
+  if (h->world > 1 || h->nparts > 1) return fail(MFEA_ESTATE, "mfea_set_grip_field: one partition per handle");
+  const size_t n = (size_t)3 * h->N;
+  std::vector<double> f;
+  if (field) {
+    f.resize(n);
+    for (size_t k = 0; k < n; ++k) {
+      if (!std::isfinite(field[k])) return fail(MFEA_EINVAL, "mfea_set_grip_field: every entry must be finite");
+      f[k] = field[k] + 0.0;  // (a −0 entry is stored as 0, as the directions are)
     }
-  if (lane_dofs(h) != nd0) {
-    if (!h->dirty && h->has_mesh && h->Ecount) RC(gather_active(h, h->active_host));
-    h->dirty = true;
   }
+  if (h->has_field == (field != nullptr) &&
+      (!field || n == 0 || std::memcmp(f.data(), h->field.data(), n * sizeof(double)) == 0))
+    return 0;
+  RC(set_device(h));
+  const int nd0 = lane_dofs(h);
+  if (h->stream) HIPC(hipStreamSynchronize(h->stream));
+  h->field.swap(f);
+  h->has_field = field != nullptr;
+  RC(grip_changed(h, nd0));
+  if (h->has_field && !h->dirty && h->parts.size() == 1) RC(upload_field(h, part0(h)));
+  return 0;
+}
+
+int mfea_get_grip_field(mfea_handle* h, double* field, int32_t* is_set) {
+  if (!h) return fail(MFEA_EINVAL, "NULL handle");
+  if (!h->has_mesh) return fail(MFEA_ESTATE, "no mesh: call mfea_set_mesh first");
+  if (is_set) *is_set = h->has_field ? 1 : 0;
+  if (!field) return 0;
+  if (h->has_field) {
+    std::copy(h->field.begin(), h->field.end(), field);
+    return 0;
+  }
+  std::fill(field, field + 3 * h->N, 0.0);
+  for (const int64_t n : h->top)
+    for (int c = 0; c < 3; ++c) field[3 * n + c] = h->grip.top[c];
+  for (const int64_t n : h->bot)
+    for (int c = 0; c < 3; ++c) field[3 * n + c] = h->grip.bot[c];
   return 0;
 }
 
@@ -4079,6 +4174,41 @@ int mfea_get_reaction(mfea_handle* h, double top[3], double bot[3]) {
                      nullptr);
     HIPC(hipGetLastError());
     HIPC(hmemcpy(h, out[b], pt.red.ptr + 9 + 3 * b, 3 * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  return 0;
+}
+
+// The generalised force of each band (states and launches as mfea_get_reaction):
+// under a grip field Σ d·f of the band's rows, one launch per band; without,
+// the band's reaction vector and its product with the band's direction — the
+// post's launch and, for the top band, its bits.  Outputs in a buffer of the
+// call's own; the post's partials and ticket set, behind the post on the stream.
+int mfea_get_grip_work(mfea_handle* h, double* top, double* bot) {
+  if (!h) return fail(MFEA_EINVAL, "NULL handle");
+  RC(set_device(h));
+  RC(ensure_built(h));
+  if (partitioned(h)) return fail(MFEA_ESTATE, "mfea_get_grip_work: one partition per handle");
+  if (!h->assembled) return fail(MFEA_ESTATE, "mfea_get_grip_work: no assembly since the last build");
+  Part& pt = part0(h);
+  const Pattern& P = pt.P;
+  hipStream_t s = h->stream;
+  HIPC(pt.gw_red.alloc(4));
+  const int64_t row0[2] = {P.n_free, P.n_free + P.n_top};
+  const int64_t nrows[2] = {P.n_top, P.n_nodes - P.n_ghost - P.n_free - P.n_top};
+  const double* const dir[2] = {h->grip.top, h->grip.bot};
+  double* const out[2] = {top, bot};
+  for (int b = 0; b < 2; ++b) {
+    if (!out[b]) continue;
+    if (h->has_field)
+      launch_reaction_field(s, row0[b], nrows[b], P.n_nodes, pt.slice_ptr.ptr, pt.row_len.ptr, pt.s_col.ptr,
+                            pt.val.ptr, pt.diag.ptr, pt.G, pt.x.ptr, pt.partials.ptr, tix(pt, 3), pt.gw_red.ptr + 3,
+                            pt.grip_d.ptr + 3 * (row0[b] - P.n_free));
+    else
+      launch_reaction3(s, row0[b], nrows[b], P.n_nodes, pt.slice_ptr.ptr, pt.row_len.ptr, pt.s_col.ptr, pt.val.ptr,
+                       pt.diag.ptr, pt.G, pt.x.ptr, pt.partials.ptr, tix(pt, 3), pt.gw_red.ptr, dir[b],
+                       pt.gw_red.ptr + 3);
+    HIPC(hipGetLastError());
+    HIPC(hmemcpy(h, out[b], pt.gw_red.ptr + 3, sizeof(double), hipMemcpyDeviceToHost));
   }
   return 0;
 }
@@ -4219,6 +4349,12 @@ int mfea_set_mesh(mfea_handle* h, int64_t n_nodes, const double* xyz, int64_t n_
   h->act_all = false;
   h->active_host.clear();
   clear_props(h);  // (indexed by the old mesh's elements)
+  if (h->has_field) {  // (... the grip field by its nodes: cleared, as mfea_set_grip_field(h, NULL))
+    if (h->stream) HIPC(hipStreamSynchronize(h->stream));
+    h->field.clear();
+    h->has_field = false;
+    RC(grip_changed(h, lane_dofs(h)));
+  }
   h->planar = true;
   for (int64_t n = 0; n < n_nodes; ++n)
     if (xyz[3 * n + 2] != 0.0) h->planar = false;
@@ -4347,7 +4483,7 @@ static int step_impl(mfea_handle* h, double dy_top, double dy_bot, const mfea_so
     if (fuse_rhs && !(h->opt_amg_start && o.precond == MFEA_PC_GAMG)) {
       Part& pt = part0(h);
       launch_cg_rhs(s, sell_op(pt), pt.code.ptr, dy_top, dy_bot, o.reg, 2, cg_vecs(pt), pt.partials.ptr, tix(pt, 0),
-                    pt.red.ptr, h->grip_arg());
+                    pt.red.ptr, h->grip_arg(), field_arg(h, pt));
       HIPC(hipGetLastError());
       h->rhs_fused = true;
       h->rhs_dy[0] = dy_top;

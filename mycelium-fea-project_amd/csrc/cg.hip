@@ -68,6 +68,7 @@ __device__ __forceinline__ void store3(double* __restrict__ v, int64_t row, cons
 // every Krylov vector and M⁻¹ = 0, so gathers across the boundary read zeros.
 // GM = GripVec (kernels.hpp): known rows x = p = fl(dy · direction), and a
 // known neighbour's whole block, b −= V p (grip_mac).
+// GM = GripField: the same with p per known row, fl(dy of its class · its vector).
 // ---------------------------------------------------------------------------
 template <bool BLOCK, class GM>
 __global__ __launch_bounds__(kBlock) void k_cg_rhs(SellOp op, const uint8_t* __restrict__ code,
@@ -78,6 +79,7 @@ __global__ __launch_bounds__(kBlock) void k_cg_rhs(SellOp op, const uint8_t* __r
   double acc[2] = {0.0, 0.0};  // b·b, u₀·u₀
   const double zero[3] = {0.0, 0.0, 0.0};
   constexpr bool VEC = std::is_same<GM, GripVec>::value;
+  constexpr bool FLD = std::is_same<GM, GripField>::value;
   GripP gp{};
   if constexpr (VEC) gp = grip_disp(g, dy_top, dy_bot);
   if (row < op.nf) {
@@ -94,6 +96,15 @@ __global__ __launch_bounds__(kBlock) void k_cg_rhs(SellOp op, const uint8_t* __r
 #pragma unroll
           for (int c = 0; c < 6; ++c) V[c] = op.val[(int64_t)c * G + idx];
           grip_of(gp, code[j], pk);
+          grip_mac(V, pk, k3);
+          kx = k3[0];
+          ky = k3[1];
+          kz = k3[2];
+        } else if constexpr (FLD) {
+          double V[6], pk[3], k3[3] = {kx, ky, kz};
+#pragma unroll
+          for (int c = 0; c < 6; ++c) V[c] = op.val[(int64_t)c * G + idx];
+          grip_of(g, j, op.nf, code[j], dy_top, dy_bot, pk);
           grip_mac(V, pk, k3);
           kx = k3[0];
           ky = k3[1];
@@ -139,6 +150,7 @@ __global__ __launch_bounds__(kBlock) void k_cg_rhs(SellOp op, const uint8_t* __r
     // ghost free rows (3) hold 0 until the solve's displacement halo fills them
     double xk[3] = {0.0, code[row] == 3 ? 0.0 : (code[row] == 2 ? dy_bot : dy_top), 0.0};
     if constexpr (VEC) grip_of(gp, code[row], xk);
+    if constexpr (FLD) grip_of(g, row, op.nf, code[row], dy_top, dy_bot, xk);
     store3(v.x, row, xk);
     store3(v.p, row, zero);
     for (int b = 0; b < 2; ++b) {
@@ -174,13 +186,15 @@ __global__ __launch_bounds__(kBlock) void k_amg_rhs(SellOp op, const uint8_t* __
   if constexpr (VEC) gp = grip_disp(g, dy_top, dy_bot);
   if (row < op.nf) {
     double b[3];
-    amg_rhs_row<GM>(op, code, dy_top, dy_bot, row, b, &gp);
+    if constexpr (std::is_same<GM, GripField>::value) amg_rhs_row<GM>(op, code, dy_top, dy_bot, row, b, nullptr, g.d);
+    else amg_rhs_row<GM>(op, code, dy_top, dy_bot, row, b, &gp);
     store3(v.r[0], row, b);
 #pragma unroll
     for (int a = 0; a < 3; ++a) acc[0] = fma(b[a], b[a], acc[0]);
   } else if (row < op.N) {
     double xk[3] = {0.0, code[row] == 3 ? 0.0 : (code[row] == 2 ? dy_bot : dy_top), 0.0};
     if constexpr (VEC) grip_of(gp, code[row], xk);
+    if constexpr (std::is_same<GM, GripField>::value) grip_of(g, row, op.nf, code[row], dy_top, dy_bot, xk);
     store3(v.x, row, xk);
   }
   block_publish<2>(acc, partials, ticket, red_out);
@@ -497,8 +511,21 @@ __global__ void k_cg_advance(int chunk, int shift, Slot* slots, SolveState* st, 
 // ---------------------------------------------------------------------------
 void launch_cg_rhs(hipStream_t s, const SellOp& op, const uint8_t* code, double dy_top,
                    double dy_bot, double reg, int precond, const CgVecs& v, double* partials,
-                   unsigned* ticket, double* red_out, const GripVec* grip) {
+                   unsigned* ticket, double* red_out, const GripVec* grip, const double* field) {
   const dim3 grid((unsigned)grid_rows(op.N > 0 ? op.N : 1));
+  if (field) {  // (a grip field: before the directions)
+    const GripField f{field};
+    if (precond == 2)
+      hipLaunchKernelGGL(k_amg_rhs<GripField>, grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials, ticket,
+                         red_out, f);
+    else if (precond == 1)
+      hipLaunchKernelGGL((k_cg_rhs<true, GripField>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, reg, v,
+                         partials, ticket, red_out, f);
+    else
+      hipLaunchKernelGGL((k_cg_rhs<false, GripField>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, reg, v,
+                         partials, ticket, red_out, f);
+    return;
+  }
   if (grip) {  // (the directions other than the tensile test's)
     if (precond == 2)
       hipLaunchKernelGGL(k_amg_rhs<GripVec>, grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials, ticket,

@@ -270,6 +270,28 @@ __device__ __forceinline__ void grip_of(const GripP& p, uint8_t code, double x[3
 #pragma unroll
   for (int c = 0; c < 3; ++c) x[c] = code == 3 ? 0.0 : (code == 2 ? p.bot[c] : p.top[c]);
 }
+// Grip field (kernels.hpp GripField): the prescribed displacement of known row
+// `row` of class `code` (3: 0) from its vector d = g.d + 3·(row − nf) —
+// p[c] = fl(amp · d[c]), amp by the class, one product per component
+__device__ __forceinline__ double grip_amp(uint8_t code, double dy_top, double dy_bot) {
+  return code == 2 ? dy_bot : dy_top;
+}
+__device__ __forceinline__ void grip_of(const double d[3], uint8_t code, double dy_top, double dy_bot, double x[3]) {
+  const double amp = grip_amp(code, dy_top, dy_bot);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) x[c] = code == 3 ? 0.0 : amp * d[c];
+}
+__device__ __forceinline__ void grip_of(const GripField& g, int64_t row, int64_t nf, uint8_t code, double dy_top,
+                                        double dy_bot, double x[3]) {
+  const double d[3] = {g.d[3 * (row - nf)], g.d[3 * (row - nf) + 1], g.d[3 * (row - nf) + 2]};
+  grip_of(d, code, dy_top, dy_bot, x);
+}
+// the generalised force of one row: w = (d·f), f64 products and sums in this
+// order, nothing fused (k_reaction<GripField>, k_event_scan<·, GripField>)
+__device__ __forceinline__ double grip_work_row(const double* __restrict__ d, const double f[3]) {
+  return (d[0] * f[0] + d[1] * f[1]) + d[2] * f[2];
+}
+
 // k += V p with V a known neighbour's symmetric block (v0..v5): the RHS term of
 // every GripVec kernel, each row's three terms in component order
 __device__ __forceinline__ void grip_mac(const double v[6], const double p[3], double k[3]) {
@@ -282,13 +304,55 @@ __device__ __forceinline__ void grip_mac(const double v[6], const double p[3], d
 // k_amg_start, amg.hip).  A row's slots in batches of four: columns, then
 // their codes, then the known couplings; b's terms in slot order.
 // GM = GripVec (p: the two prescribed displacements): the whole block, grip_mac.
+// GM = GripField (fd: the field's rows): the same with p per neighbour — the
+// vectors of a batch's four neighbours loaded together after the codes, every
+// load unconditional on an index clamped into the known rows, the class applied
+// after (a guarded load would serialise the batch).
 template <class GM = GripY>
 __device__ __forceinline__ void amg_rhs_row(const SellOp& op, const uint8_t* __restrict__ code, double dy_top,
-                                            double dy_bot, int64_t row, double b[3], const GripP* p = nullptr) {
+                                            double dy_bot, int64_t row, double b[3], const GripP* p = nullptr,
+                                            const double* __restrict__ fd = nullptr) {
   const int64_t base = (int64_t)op.slice_ptr[row >> 6] * 64 + (row & 63);
   const int len = op.row_len[row];
   const int64_t G = op.G;
   double kx = 0.0, ky = 0.0, kz = 0.0;
+  if constexpr (std::is_same<GM, GripField>::value) {
+    double k3[3] = {0.0, 0.0, 0.0};
+    constexpr int U = 4;
+    for (int k0 = 0; k0 < len; k0 += U) {
+      int64_t idx[U];
+      int32_t j[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        idx[u] = base + (int64_t)(k0 + u < len ? k0 + u : k0) * 64;
+        j[u] = k0 + u < len ? op.s_col[idx[u]] : 0;
+      }
+      uint8_t c[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) c[u] = k0 + u < len && j[u] >= op.nf ? code[j[u]] : 3;
+      double dj[U][3];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t kk = j[u] >= op.nf ? (int64_t)j[u] - op.nf : 0;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) dj[u][a] = fd[3 * kk + a];
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if (c[u] != 3) {
+          double v[6], pk[3];
+#pragma unroll
+          for (int q = 0; q < 6; ++q) v[q] = op.val[(int64_t)q * G + idx[u]];
+          grip_of(dj[u], c[u], dy_top, dy_bot, pk);
+          grip_mac(v, pk, k3);
+        }
+      }
+    }
+    b[0] = 0.0 - k3[0];
+    b[1] = 0.0 - k3[1];
+    b[2] = 0.0 - k3[2];
+    return;
+  }
   if constexpr (std::is_same<GM, GripVec>::value) {
     double k3[3] = {0.0, 0.0, 0.0};
     constexpr int U = 4;

@@ -73,6 +73,8 @@ __device__ __forceinline__ double block_max(double v, double* lds) {
 // min in place of the max, through the same publish.
 // GM = GripVec (q.vec): the row blocks run k_reaction<GripVec>'s body — the
 // reaction vector into q.sums, F₁ along q.w into force_out, the same bits.
+// GM = GripField (q.field): k_reaction<GripField>'s body — F₁ = Σ w_r of the top
+// rows into force_out through the scalar publish, the same bits.
 // ---------------------------------------------------------------------------
 template <bool PS, class GM>
 __global__ __launch_bounds__(kBlock) void k_event_scan(EventScan q) {
@@ -84,6 +86,16 @@ __global__ __launch_bounds__(kBlock) void k_event_scan(EventScan q) {
       if (t < q.nrows)
         reaction_row3(q.row0 + t, q.N, q.slice_ptr, q.row_len, q.s_col, q.val, q.diag, q.G, q.u, f3);
       reaction3_publish(f3, q.partials_r, q.ticket_r, q.sums, q.w, q.force_out, q.grid_r, blockIdx.x);
+      return;
+    }
+    if constexpr (std::is_same<GM, GripField>::value) {
+      double w[1] = {0.0};
+      if (t < q.nrows) {
+        double f3[3];
+        reaction_row3(q.row0 + t, q.N, q.slice_ptr, q.row_len, q.s_col, q.val, q.diag, q.G, q.u, f3);
+        w[0] = grip_work_row(q.field + 3 * t, f3);
+      }
+      block_publish_as<1>(w, q.partials_r, q.ticket_r, q.force_out, q.grid_r, blockIdx.x);
       return;
     }
     double f[1] = {0.0};
@@ -221,6 +233,7 @@ __global__ __launch_bounds__(kBlock) void k_event_unfail(const int32_t* __restri
 }  // namespace
 
 void launch_event_scan(hipStream_t s, EventScan q) {
+  if (q.field) q.vec = false;  // (a grip field: one sum, the scalar partial area)
   q.grid_r = (unsigned)grid_rows(q.nrows > 0 ? q.nrows : 1);
   q.grid_e = (unsigned)grid_rows(q.E > 0 ? q.E : 1);
   // the two row sets reduce side by side: disjoint partials
@@ -228,6 +241,11 @@ void launch_event_scan(hipStream_t s, EventScan q) {
   q.partials_e = q.partials_r + (q.vec ? 3 : 1) * (q.grid_r + kShards);  // (three sums: three times the room)
   q.pmax = q.partials_e + (q.grid_e + kShards);
   const dim3 g(q.grid_r + q.grid_e);
+  if (q.field) {
+    if (q.strength) hipLaunchKernelGGL((k_event_scan<true, GripField>), g, dim3(kBlock), 0, s, q);
+    else hipLaunchKernelGGL((k_event_scan<false, GripField>), g, dim3(kBlock), 0, s, q);
+    return;
+  }
   if (q.vec) {
     if (q.strength) hipLaunchKernelGGL((k_event_scan<true, GripVec>), g, dim3(kBlock), 0, s, q);
     else hipLaunchKernelGGL((k_event_scan<false, GripVec>), g, dim3(kBlock), 0, s, q);

@@ -73,6 +73,10 @@ __device__ __forceinline__ void bar_block(double vx, double vy, double vz, doubl
 // GM: GripY, or GripVec with gp the launch's two prescribed displacements — a
 // known neighbour's whole block then (grip_mac), the class still from the row
 // position and inside the batch as before.
+// GM = GripField (q->field): the same with p per neighbour, amplitude by the
+// class.  The neighbour's vector is three more loads of the batch's second
+// group, unconditional like the rest: on the index clamped to the first known
+// row when the neighbour is free, the class applied afterwards.
 template <class M, class GM = GripY>
 __device__ __forceinline__ void assemble_row(int64_t N, int64_t row, const double* __restrict__ xyz,
                                              const int32_t* __restrict__ slice_ptr,
@@ -83,6 +87,7 @@ __device__ __forceinline__ void assemble_row(int64_t N, int64_t row, const doubl
                                              int64_t G, double* __restrict__ val, double* __restrict__ diag,
                                              const AsmRhs* q, double* k3, const GripP* gp = nullptr) {
   constexpr bool PE = !std::is_same<M, Material>::value;
+  constexpr bool FLD = std::is_same<GM, GripField>::value;
   const bool rhs = q != nullptr && row < q->nf;
   const int64_t base = (int64_t)slice_ptr[row >> 6] * 64 + (row & 63);
   const int len = row_len[row];
@@ -117,9 +122,15 @@ __device__ __forceinline__ void assemble_row(int64_t N, int64_t row, const doubl
     // with the activity and the coordinates, so the batch still waits for two
     // dependent round trips, not three
     double2 se[PE ? U : 1];
+    double dj[FLD ? U : 1][3];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       if constexpr (PE) se[u] = section_of(m, e[u]);
+      if constexpr (FLD) {
+        const int64_t kk = j[u] >= q->nf ? (int64_t)j[u] - q->nf : 0;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) dj[u][a] = q->field[3 * kk + a];
+      }
       const uint8_t av = active[e[u]];
       act[u] = ok[u] ? av : 0;
       // the neighbour's class from its row position (no load: a select on a
@@ -149,6 +160,10 @@ __device__ __forceinline__ void assemble_row(int64_t N, int64_t row, const doubl
         if constexpr (std::is_same<GM, GripVec>::value) {
           double pk[3];
           grip_of(*gp, cd[u], pk);
+          grip_mac(v, pk, k3);
+        } else if constexpr (FLD) {
+          double pk[3];
+          grip_of(dj[u], cd[u], q->dy_top, q->dy_bot, pk);
           grip_mac(v, pk, k3);
         } else {
           const double dy = cd[u] == 2 ? q->dy_bot : q->dy_top;
@@ -294,6 +309,8 @@ __global__ __launch_bounds__(kBlock) void k_assemble(int64_t N, const double* __
         const uint8_t c = q.code[row];
         double xk[3] = {0.0, c == 3 ? 0.0 : (c == 2 ? q.dy_bot : q.dy_top), 0.0};
         if constexpr (VEC) grip_of(gp, c, xk);
+        if constexpr (std::is_same<GM, GripField>::value)
+          grip_of(GripField{q.field}, row, q.nf, c, q.dy_top, q.dy_bot, xk);
 #pragma unroll
         for (int a = 0; a < 3; ++a) q.x[3 * row + a] = xk[a];
       }
@@ -321,6 +338,7 @@ __global__ __launch_bounds__(kBlock) void k_rhs_init(
   const int64_t row = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   double acc[3] = {0.0, 0.0, 0.0};  // r·z, b·b, z·z
   constexpr bool VEC = std::is_same<GM, GripVec>::value;
+  constexpr bool FLD = std::is_same<GM, GripField>::value;
   GripP gp{};
   if constexpr (VEC) gp = grip_disp(g, dy_top, dy_bot);
   if (row < nf) {
@@ -336,6 +354,15 @@ __global__ __launch_bounds__(kBlock) void k_rhs_init(
 #pragma unroll
           for (int c = 0; c < 6; ++c) v[c] = val[(int64_t)c * G + idx];
           grip_of(gp, code[j], pk);
+          grip_mac(v, pk, k3);
+          kx = k3[0];
+          ky = k3[1];
+          kz = k3[2];
+        } else if constexpr (FLD) {  // ... with p of this neighbour
+          double v[6], pk[3], k3[3] = {kx, ky, kz};
+#pragma unroll
+          for (int c = 0; c < 6; ++c) v[c] = val[(int64_t)c * G + idx];
+          grip_of(g, j, nf, code[j], dy_top, dy_bot, pk);
           grip_mac(v, pk, k3);
           kx = k3[0];
           ky = k3[1];
@@ -378,6 +405,11 @@ __global__ __launch_bounds__(kBlock) void k_rhs_init(
     if constexpr (VEC) {
       double xk[3];
       grip_of(gp, code[row], xk);
+#pragma unroll
+      for (int a = 0; a < 3; ++a) x[3 * row + a] = xk[a];
+    } else if constexpr (FLD) {
+      double xk[3];
+      grip_of(g, row, nf, code[row], dy_top, dy_bot, xk);
 #pragma unroll
       for (int a = 0; a < 3; ++a) x[3 * row + a] = xk[a];
     } else {
@@ -584,6 +616,9 @@ __global__ void k_advance(int chunk, Slot* slots, SolveState* st) {
 // and the work-conjugate force along g.top into red_out (NULL: the sums alone;
 // the bottom band of mfea_get_reaction), formed by the block that ends the
 // reduction: F = (t₀·S₀ + t₁·S₁) + t₂·S₂.
+// GM = GripField (g.d: the vector of row row0, the band's first): the same
+// row body, then the row's generalised force w = (d₀·f₀ + d₁·f₁) + d₂·f₂ — one
+// sum through the tensile reaction's publish into red_out.
 // ---------------------------------------------------------------------------
 template <class GM>
 __global__ __launch_bounds__(kBlock) void k_reaction(int64_t row0, int64_t nrows, int64_t N,
@@ -599,6 +634,16 @@ __global__ __launch_bounds__(kBlock) void k_reaction(int64_t row0, int64_t nrows
     double f3[3] = {0.0, 0.0, 0.0};
     if (t < nrows) reaction_row3(row0 + t, N, slice_ptr, row_len, s_col, val, diag, G, u, f3);
     reaction3_publish(f3, partials, ticket, sums, g.top, red_out, gridDim.x, blockIdx.x);
+    return;
+  }
+  if constexpr (std::is_same<GM, GripField>::value) {
+    double w[1] = {0.0};
+    if (t < nrows) {
+      double f3[3];
+      reaction_row3(row0 + t, N, slice_ptr, row_len, s_col, val, diag, G, u, f3);
+      w[0] = grip_work_row(g.d + 3 * t, f3);
+    }
+    block_publish<1>(w, partials, ticket, red_out);
     return;
   }
   double f[1] = {0.0};
@@ -975,7 +1020,13 @@ void launch_assemble(hipStream_t s, int64_t N, const double* xyz, const int32_t*
                      const AsmRhs* rhs, const double2* sec) {
   const ElemSection ms{sec};
   if (rhs) {  // (the reduction's blocks publish even when N = 0)
-    if (rhs->vec && sec)
+    if (rhs->field && sec)
+      hipLaunchKernelGGL((k_assemble<true, ElemSection, GripField>), MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, xyz,
+                         slice_ptr, row_len, s_col, s_elem, active, ms, G, val, diag, *rhs);
+    else if (rhs->field)
+      hipLaunchKernelGGL((k_assemble<true, Material, GripField>), MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, xyz,
+                         slice_ptr, row_len, s_col, s_elem, active, m, G, val, diag, *rhs);
+    else if (rhs->vec && sec)
       hipLaunchKernelGGL((k_assemble<true, ElemSection, GripVec>), MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, xyz,
                          slice_ptr, row_len, s_col, s_elem, active, ms, G, val, diag, *rhs);
     else if (rhs->vec)
@@ -1029,8 +1080,13 @@ void launch_rhs_init(hipStream_t s, int64_t N, int64_t nf, const int32_t* slice_
                      const int32_t* row_len, const int32_t* s_col, const double* val,
                      const double* diag, int64_t G, const uint8_t* code, double dy_top,
                      double dy_bot, double reg, int precond, double* x, double* r, double* p,
-                     double* dinv, double* partials, unsigned* ticket, double* red_out, const GripVec* grip) {
-  if (grip)
+                     double* dinv, double* partials, unsigned* ticket, double* red_out, const GripVec* grip,
+                     const double* field) {
+  if (field)
+    hipLaunchKernelGGL(k_rhs_init<GripField>, MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, nf, slice_ptr, row_len, s_col,
+                       val, diag, G, code, dy_top, dy_bot, reg, precond, x, r, p, dinv, partials, ticket, red_out,
+                       GripField{field});
+  else if (grip)
     hipLaunchKernelGGL(k_rhs_init<GripVec>, MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, nf, slice_ptr, row_len, s_col,
                        val, diag, G, code, dy_top, dy_bot, reg, precond, x, r, p, dinv, partials, ticket, red_out,
                        *grip);
@@ -1096,6 +1152,15 @@ void launch_reaction3(hipStream_t s, int64_t row0, int64_t nrows, int64_t N, con
   for (int c = 0; c < 3 && w; ++c) g.top[c] = w[c];
   hipLaunchKernelGGL(k_reaction<GripVec>, MFEA_GRID(grid_rows(nrows > 0 ? nrows : 1)), row0, nrows, N, slice_ptr,
                      row_len, s_col, val, diag, G, u, partials, ticket, w ? force_out : nullptr, g, sums);
+}
+
+void launch_reaction_field(hipStream_t s, int64_t row0, int64_t nrows, int64_t N, const int32_t* slice_ptr,
+                           const int32_t* row_len, const int32_t* s_col, const double* val, const double* diag,
+                           int64_t G, const double* u, double* partials, unsigned* ticket, double* red_out,
+                           const double* field_rows) {
+  hipLaunchKernelGGL(k_reaction<GripField>, MFEA_GRID(grid_rows(nrows > 0 ? nrows : 1)), row0, nrows, N, slice_ptr,
+                     row_len, s_col, val, diag, G, u, partials, ticket, red_out, GripField{field_rows},
+                     (double*)nullptr);
 }
 
 void launch_stress(hipStream_t s, int64_t E, const int32_t* e2n, const double* xyz,

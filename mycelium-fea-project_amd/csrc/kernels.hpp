@@ -102,9 +102,19 @@ struct ElemPost {
 // symmetric block of a known neighbour, b −= V·p, and a known row x = p.  The
 // kernels are templates over the two (no run-time choice inside them); a
 // launcher picks GripVec when its `grip` argument is non-null.
+// GripField (mfea_set_grip_field): a vector per grip node instead of one per
+// band — d holds 3 doubles per known row in Pattern row order, row j at
+// d[3·(j − nf)], and the prescribed displacement of row j is
+// p[c] = fl(amp · d[3·(j − nf) + c]) with amp the amplitude of the row's class
+// (dy_bot for a bottom row, dy_top for a top row).  The RHS term and the known
+// rows' x are GripVec's with p per row.  A launcher picks GripField when its
+// `field` argument is non-null, before it looks at `grip`.
 struct GripY {};
 struct GripVec {
   double top[3], bot[3];
+};
+struct GripField {
+  const double* d;
 };
 
 // ---- launchers (defined in kernels.hip) -------------------------------------
@@ -118,6 +128,9 @@ struct AsmRhs {
   // the grip directions (vec: other than the tensile test's — the GripVec kernel)
   GripVec grip;
   bool vec;
+  // a grip field (non-null: the GripField kernel, whatever vec says): 3 doubles
+  // per known row, at least 3 readable
+  const double* field;
   // row classes by position (symbolic.hpp Pattern): top grip rows
   // [nf, top_end), bottom rows [top_end, bot_end), ghost rows after
   int64_t top_end, bot_end;
@@ -152,7 +165,7 @@ void launch_rhs_init(hipStream_t s, int64_t N, int64_t nf, const int32_t* slice_
                      const double* diag, int64_t G, const uint8_t* code, double dy_top,
                      double dy_bot, double reg, int precond, double* x, double* r, double* p,
                      double* dinv, double* partials, unsigned* ticket, double* red_out,
-                     const GripVec* grip = nullptr);
+                     const GripVec* grip = nullptr, const double* field = nullptr);
 
 void launch_init_finalize(hipStream_t s, const double* red, double rtol, double atol, int norm,
                           int max_it, double reg, Slot* slots, SolveState* st);
@@ -186,6 +199,15 @@ void launch_reaction3(hipStream_t s, int64_t row0, int64_t nrows, int64_t N, con
                       const int32_t* row_len, const int32_t* s_col, const double* val, const double* diag,
                       int64_t G, const double* u, double* partials, unsigned* ticket, double* sums,
                       const double* w, double* force_out);
+// The generalised force of a band under a grip field: red_out[0] = Σ over rows
+// [row0, row0 + nrows) of w_r = (d[0]·f[0] + d[1]·f[1]) + d[2]·f[2], f = (K·U)
+// of the row as launch_reaction3 forms it, d = field_rows[3·(row − row0)..] (the
+// band's first row of the field).  f64, nothing fused; the rows reduced in
+// launch_reaction's fixed order, one launch, launch_reaction's partials.
+void launch_reaction_field(hipStream_t s, int64_t row0, int64_t nrows, int64_t N, const int32_t* slice_ptr,
+                           const int32_t* row_len, const int32_t* s_col, const double* val, const double* diag,
+                           int64_t G, const double* u, double* partials, unsigned* ticket, double* red_out,
+                           const double* field_rows);
 
 // owned (multi-partition): count only elements this partition reports; NULL = all.
 // fail_list / fail_cnt: the (owned) elements that fail in this launch are
@@ -246,6 +268,10 @@ struct EventScan {
   bool vec;
   double w[3];
   double* sums;
+  // field (non-null; vec is then not read): the top rows' vectors of a grip
+  // field — force_out = Σ w_r, launch_reaction_field's expression and bits, the
+  // partial area the scalar one
+  const double* field;
 };
 void launch_event_scan(hipStream_t s, EventScan q);
 int64_t event_scan_partials(int64_t n_top, int64_t n_elems, bool vec = false);
@@ -310,7 +336,8 @@ void launch_spmv_csr(hipStream_t s, int j, int64_t n, const int64_t* indptr,
 // known rows' x only, u₀·u₀ = 0).
 void launch_cg_rhs(hipStream_t s, const SellOp& op, const uint8_t* code, double dy_top,
                    double dy_bot, double reg, int precond, const CgVecs& v, double* partials,
-                   unsigned* ticket, double* red_out, const GripVec* grip = nullptr);
+                   unsigned* ticket, double* red_out, const GripVec* grip = nullptr,
+                   const double* field = nullptr);
 // part: 2 parity buffers × [4][kCgMaxPartials] block partials (cg.hip)
 constexpr int kCgMaxPartials = 512;
 // k_cg_first: w₀ = A u₀; block partials (γ₀, δ₀, r·r, u·u) → part parity 0;

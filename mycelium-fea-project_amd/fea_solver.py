@@ -237,10 +237,35 @@ def parse_grip_direction(text):
 TENSILE = (0.0, 1.0, 0.0)
 
 
+def complete_grip_field(grip_field, n_nodes, top, bot, grip_direction=None):
+    """The n_nodes x 3 field Engine.set_grip_field takes, from fea_solver's
+    grip_field argument: a CSV path (mfea.fields.read_csv), a (field, listed)
+    pair, or an n_nodes x 3 array (every node listed).  A grip node that is not
+    listed takes its band's direction vector — grip_direction's, or the tensile
+    default; a node in both bands the bottom one's."""
+    from mfea import fields
+    if isinstance(grip_field, (str, os.PathLike)):
+        grip_field = fields.read_csv(grip_field, n_nodes)
+    if isinstance(grip_field, tuple):
+        field, listed = grip_field
+    else:
+        field, listed = grip_field, np.ones(n_nodes, dtype=bool)
+    field = np.array(field, dtype=np.float64).reshape(-1, 3)
+    listed = np.asarray(listed, dtype=bool).ravel()
+    if field.shape[0] != n_nodes or listed.size != n_nodes:
+        raise ValueError(f"grip_field must have one row per node ({n_nodes})")
+    vt, vb = grip_direction if grip_direction is not None else (TENSILE, TENSILE)
+    for nodes, vec in ((top, vt), (bot, vb)):  # (bottom last: it wins)
+        nodes = np.asarray(nodes, dtype=np.int64)
+        rest = nodes[~listed[nodes]]
+        field[rest] = np.asarray(vec, dtype=np.float64)
+    return field
+
+
 def fea_solver(results_dir, tol=GRIP_LENGTH, *, rtol=None, max_it=None, precond=None,
                out_format="python", verbose=True, nparts=1, npy=False, device_run=False,
                events=False, tie_rtol=1e-9, max_events=None, element_props=None, grip_direction=None,
-               energy=False):
+               energy=False, grip_field=None):
     """The reference step loop (src/fea_solver.py:186-335) with the hot path on device.
 
     Reads <results_dir>/nodes.csv + elements.csv, runs N_STEPS load steps and
@@ -287,6 +312,18 @@ def fea_solver(results_dir, tol=GRIP_LENGTH, *, rtol=None, max_it=None, precond=
     ramp, device_run, events and element_props; force_displacement.csv keeps its
     two columns, the amplitude span and the work-conjugate force.
 
+    grip_field (one process, one partition): a CSV file with the columns
+    node_id,dx,dy,dz (mfea.fields.read_csv), a (field, listed) pair or an
+    n_nodes x 3 array — a prescribed vector per grip node
+    (Engine.set_grip_field): grip node n moves by amplitude · d_n, the amplitude
+    being dy_top, or dy_bot for a bottom node.  A grip rotation, an affine
+    boundary displacement, an indentation.  Grip nodes the file does not list
+    take their band's direction vector (grip_direction's, or the tensile
+    default); free nodes it lists are ignored.  Works with the ramp, device_run,
+    events, element_props, energy and grip_direction.  force_displacement.csv
+    keeps total_displacement = dy_top − dy_bot; total_force is the generalised
+    force of the top band, Σ d_n·(K U)_n over its nodes.
+
     energy=True (one process, one partition): the strain energy of every record
     row, split into its axial and bending parts (Engine.energy /
     mfea_get_energy), each row on the activity its K was assembled from — the
@@ -306,6 +343,8 @@ def fea_solver(results_dir, tol=GRIP_LENGTH, *, rtol=None, max_it=None, precond=
         raise ValueError("grip_direction needs one process and one partition (world == 1, nparts == 1)")
     if isinstance(grip_direction, str):
         grip_direction = parse_grip_direction(grip_direction)
+    if grip_field is not None and (world > 1 or nparts > 1):
+        raise ValueError("grip_field needs one process and one partition (world == 1, nparts == 1)")
     if element_props is not None and (world > 1 or nparts > 1):
         raise ValueError("element_props needs one process and one partition (world == 1, nparts == 1)")
     if events and (world > 1 or nparts > 1):
@@ -341,6 +380,8 @@ def fea_solver(results_dir, tol=GRIP_LENGTH, *, rtol=None, max_it=None, precond=
     eng.set_mesh(coords, e2n)
     eng.set_bc(top, bot)
     eng.set_active(None)
+    if grip_field is not None:  # (set_mesh cleared the one the process-wide handle may have held)
+        eng.set_grip_field(complete_grip_field(grip_field, n_nodes, top, bot, grip_direction))
     if element_props is not None:
         props = (element_props if isinstance(element_props, dict)
                  else read_element_props(element_props, n_elems))
@@ -559,6 +600,13 @@ def main(argv=None):
     ap.add_argument("--energy", action="store_true",
                     help="also write the strain energy of every record row, axial and bending parts: energy.csv, "
                          "element_energy_axial.csv, element_energy_bending.csv (one process, one partition)")
+    ap.add_argument("--grip-field", metavar="FILE.csv", default=None,
+                    help="a prescribed vector per grip node: CSV with the header node_id,dx,dy,dz; node n moves "
+                         "by amplitude x (dx,dy,dz), the ramp's displacements being the amplitudes.  Grip nodes "
+                         "not listed take their band's direction (--grip-direction or the tensile default), "
+                         "free nodes listed are ignored.  force_displacement.csv keeps total_displacement = "
+                         "dy_top - dy_bot, total_force is the generalised force of the top band "
+                         "(one process, one partition)")
     a = ap.parse_args(argv)
     if a.energy and a.parts > 1:
         print("fea_solver: --energy needs one partition (--parts 1)", file=sys.stderr)
@@ -572,6 +620,18 @@ def main(argv=None):
             grip = parse_grip_direction("1,0,0" if a.shear else a.grip_direction)
         except ValueError as e:
             print(f"fea_solver: --grip-direction: {e}", file=sys.stderr)
+            sys.exit(2)
+    field = None
+    if a.grip_field is not None:
+        if a.parts > 1:
+            print("fea_solver: --grip-field needs one partition (--parts 1)", file=sys.stderr)
+            sys.exit(2)
+        try:
+            from mfea import fields
+            n_nodes = len(pd.read_csv(os.path.join(a.results_dir, "nodes.csv")))
+            field = fields.read_csv(a.grip_field, n_nodes)
+        except (ValueError, OSError) as e:
+            print(f"fea_solver: --grip-field: {e}", file=sys.stderr)
             sys.exit(2)
     props = None
     if a.element_props is not None:
@@ -587,7 +647,7 @@ def main(argv=None):
                         "bjacobi": _capi.PC_BLOCK_JACOBI, "sor": _capi.PC_SOR, "icc": _capi.PC_ICC}[a.pc],
                out_format=a.format, nparts=a.parts, npy=a.npy, device_run=a.device_run,
                events=a.events, tie_rtol=a.tie_rtol, max_events=a.max_events, element_props=props,
-               grip_direction=grip, energy=a.energy)
+               grip_direction=grip, energy=a.energy, grip_field=field)
 
 
 if __name__ == "__main__":

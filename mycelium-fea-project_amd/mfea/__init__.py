@@ -10,3 +10,4 @@ from ._capi import (Engine, MfeaError, SolverFailure, SolveOpts, Stats, abi_vers
                     RunRecords, RUN_COMPLETE, RUN_NO_ACTIVE,
                     EventOpts, EventOut, EventRecords, event_opts, event_envelope,
                     EVENTS_COMPLETE, EVENTS_LAMBDA_MAX, EVENTS_UNLOADED, ElementProps)
+from . import fields  # noqa: F401

@@ -127,6 +127,9 @@ _sig = {
     "mfea_set_grip_motion": (C.c_int, [_P, _P, _P]),
     "mfea_get_grip_motion": (C.c_int, [_P, _P, _P]),
     "mfea_get_reaction": (C.c_int, [_P, _P, _P]),
+    "mfea_set_grip_field": (C.c_int, [_P, _P]),
+    "mfea_get_grip_field": (C.c_int, [_P, _P, C.POINTER(C.c_int32)]),
+    "mfea_get_grip_work": (C.c_int, [_P, _P, _P]),
     "mfea_get_energy": (C.c_int, [_P, _P, _P, _P, C.POINTER(ElementEnergy)]),
     "mfea_set_mesh": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_uint32]),
     "mfea_set_bc": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P]),
@@ -547,6 +550,39 @@ class Engine:
         top, bot = np.empty(3), np.empty(3)
         _check(_lib.mfea_get_reaction(self._h, _ptr(top), _ptr(bot)))
         return top, bot
+
+    def set_grip_field(self, field=None):
+        """A prescribed vector per grip node (mfea_set_grip_field): field is
+        n_nodes x 3 in the order of the mesh's nodes, row n the vector d_n; a
+        node of the top band is prescribed dy_top * d_n, one of the bottom band
+        dy_bot * d_n.  Rows of nodes in no band are ignored.  None: no field,
+        back to set_grip_motion's two directions.  mfea.fields builds the usual
+        ones.  The library copies the array."""
+        if field is None:
+            _check(_lib.mfea_set_grip_field(self._h, None))
+            return
+        a = np.ascontiguousarray(field, dtype=np.float64)
+        if hasattr(self, "_xyz") and a.size != 3 * self.n_nodes:
+            raise ValueError(f"field must have three entries per node ({self.n_nodes} nodes)")
+        _check(_lib.mfea_set_grip_field(self._h, _ptr(a)))
+
+    def grip_field(self):
+        """(field, is_set): the stored n_nodes x 3 field; without one, every row
+        holds the vector its node's band uses (mfea_get_grip_field)."""
+        if not hasattr(self, "_xyz"):  # (no mesh yet: the library's MFEA_ESTATE)
+            _check(_lib.mfea_get_grip_field(self._h, None, None))
+        out = np.empty((self.n_nodes, 3), dtype=np.float64)
+        is_set = C.c_int32(0)
+        _check(_lib.mfea_get_grip_field(self._h, _ptr(out), C.byref(is_set)))
+        return out, bool(is_set.value)
+
+    def grip_work(self):
+        """(top, bot): the generalised force of each band on the unregularised K
+        of the last assembly and the current U (mfea_get_grip_work); the top one
+        is what a step reports as its force."""
+        top, bot = np.empty(1), np.empty(1)
+        _check(_lib.mfea_get_grip_work(self._h, _ptr(top), _ptr(bot)))
+        return float(top[0]), float(bot[0])
 
     ENERGY_ROWS = ("w_axial", "w_bending", "g_axial", "g_bending")
 
