@@ -274,6 +274,79 @@ int mfea_get_grip_field(mfea_handle* h, double* field, int32_t* is_set);
  * band those are total_force's bits. */
 int mfea_get_grip_work(mfea_handle* h, double* top, double* bot);
 
+/* ---- nodal loads: a force vector per free node, dead or proportional --------- */
+/* loads: 3·n_nodes doubles, original node order, row n = the force f_n on node
+ * n; NULL: no loads (the engine as it is without them; mode is then ignored).
+ * Copied.  Self-weight, a point or indenter force, a pre-load under a ramp, a
+ * force-controlled pull (a band held by zero rows of a grip field) are loads.
+ *   mode      MFEA_LOAD_DEAD: q_n = f_n whatever the amplitudes of the call;
+ *             MFEA_LOAD_PROPORTIONAL: q_n[c] = fl(dy_top · f_n[c]), one f64
+ *             product per component: f is the load per unit of the top amplitude.
+ *   storage   rows of grip nodes are stored and read nowhere (a prescribed DOF
+ *             has no load).  −0 is stored as 0, and a product −0 counts as 0.
+ *             An all-zero array counts as set: it takes the load kernels, and U,
+ *             iteration counts, stress, activity, n_active and force are bit for
+ *             bit those of a handle without loads.
+ *   RHS       a free row of node n takes b[c] = q[c] − k[c], k the grip term
+ *             accumulated as without loads (the fma chains of the tensile test,
+ *             mfea_set_grip_motion or mfea_set_grip_field, in slot order), the
+ *             subtraction one operation in place of 0 − k[c].  Known rows are
+ *             unchanged.  mfea_stats.bnorm and the stopping threshold are those
+ *             of this b: a dead load at dy_top = dy_bot = 0 is a real solve.
+ *   floating  a free row whose connected component of the active element graph
+ *             holds no grip row (a node with no active element included) has its
+ *             load dropped, q = 0: it stays at exactly zero for every
+ *             preconditioner and entry point, where the regularised system would
+ *             return displacements near 1e12.  The mask is that of the activity
+ *             the step's K is assembled from — the activity before that step's
+ *             failures — recomputed on the device, on the handle's stream,
+ *             whenever that activity has moved, and only while loads are set.
+ *   force     total_force, mfea_run_records.force, force1, mfea_get_reaction and
+ *             mfea_get_grip_work stay as defined: sums over grip rows of K·U.
+ *   events    proportional loads scale with the amplitude pair like every other
+ *             prescribed quantity, so U ∝ amplitude on a fixed active set and
+ *             mfea_event / mfea_run_events stand unchanged.  With dead loads the
+ *             response is affine in the load factor: both return MFEA_ESTATE.
+ *             mfea_solve, mfea_step and mfea_run work in both modes.
+ * MFEA_ESTATE before mfea_set_mesh.  MFEA_EINVAL, the handle unchanged, for an
+ * entry that is not finite or an unknown mode.
+ * Lifetime: mfea_set_mesh clears the loads (the node count changes);
+ * mfea_set_bc, mfea_set_active, mfea_set_material, mfea_set_element_props,
+ * mfea_set_grip_motion and mfea_set_grip_field keep them; they are gathered
+ * into row order again at every build.
+ * One partition only: MFEA_ESTATE on a partitioned handle; a handle with loads
+ * that is partitioned afterwards returns MFEA_ESTATE from its next build.
+ * A change — other bytes, another mode, or NULL — drops exactly what a change of
+ * the grip directions drops: the right-hand side a step cached and every
+ * captured graph, after draining the stream.  K, the symbolic hierarchy and
+ * everything option "keep_operator" keeps stay: the next step is a kept step
+ * (amg_rebuilt == 0).  Setting the same bytes and mode again drops nothing.
+ * Planar meshes (every z == 0): with any stored z entry non-zero the handle
+ * solves with 3 DOFs per node, by the rule and the rebuild of
+ * mfea_set_grip_field; clearing the loads, or setting ones with every z entry
+ * zero, goes back to 2. */
+#define MFEA_LOAD_DEAD 0
+#define MFEA_LOAD_PROPORTIONAL 1
+int mfea_set_node_loads(mfea_handle* h, const double* loads /* 3·n_nodes or NULL */, int32_t mode);
+/* loads (3·n_nodes, may be NULL) as stored, zeros when not set; *mode and
+ * *is_set (0/1) may be NULL. */
+int mfea_get_node_loads(mfea_handle* h, double* loads /* may be NULL */, int32_t* mode, int32_t* is_set);
+/* The work of the loads, L = Σ q_n·u_n over the free nodes that are not
+ * floating, each term (q[0]·u[0] + q[1]·u[1]) + q[2]·u[2] in f64 with nothing
+ * fused, the rows reduced in a fixed order (bitwise reproducible for a mesh).
+ * The amplitudes and the mask are those of the last solve, U the current one.
+ * States as mfea_get_reaction; 0.0 when no loads are set.
+ * Work identity with loads (f: the free DOFs, r = b − (K + reg·I)u_f the
+ * solver's residual): at equilibrium
+ *   u_fᵀ(KU)_f = L − reg·‖u_f‖² − u_f·r
+ * so, with G the two values of mfea_get_grip_work,
+ *   2W = dy_top·G_top + dy_bot·G_bot + L
+ * up to those two terms.  With loads the g rows of mfea_get_energy remain the
+ * partial derivatives at fixed U; they are no longer the gradient of the
+ * equilibrium energy (the loads' potential −L depends on the parameters through
+ * U as well). */
+int mfea_get_load_work(mfea_handle* h, double* work);
+
 /* ---- strain energy per element: axial and bending parts, and their gradients - */
 /* The element assembled here has two stiffness terms, k_ax = EA_e/L along the
  * filament and k_b = EI12_e/L³ across it (EA_e = E_e·A_e, EI12_e = (12·E_e)·I_e).

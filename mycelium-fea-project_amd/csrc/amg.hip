@@ -1407,13 +1407,14 @@ __global__ __launch_bounds__(kBlock) void k_amg_row0_inverse(AmgCg cg, int32_t* 
 // and the reduction's last block k_cg_init_finalize's: the state, and the
 // zeroing of the partial buffers.
 // GM: GripY, or GripVec / GripField — k_amg_rhs<GM>'s row body (kernels.hpp).
-template <int ND, class GM>
+// LD: LoadNone, or NodeLoad — k_amg_rhs<GM, LD>'s.
+template <int ND, class GM, class LD = LoadNone>
 __global__ __launch_bounds__(kBlock) void k_amg_start(SellOp op, const uint8_t* __restrict__ code, double dy_top,
                                                       double dy_bot, CgVecs v, double* partials, unsigned* ticket,
                                                       double* red_out, AmgLevD L0, AmgCg cg,
                                                       const int32_t* __restrict__ inv, double rtol, double atol,
                                                       int norm, int max_it, double reg, SolveState* st,
-                                                      double* zero, int64_t nzero, GM g) {
+                                                      double* zero, int64_t nzero, GM g, LD ld) {
   const int64_t row = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   double acc[2] = {0.0, 0.0};
   constexpr bool VEC = std::is_same<GM, GripVec>::value;
@@ -1421,8 +1422,9 @@ __global__ __launch_bounds__(kBlock) void k_amg_start(SellOp op, const uint8_t* 
   if constexpr (VEC) gp = grip_disp(g, dy_top, dy_bot);
   if (row < op.nf) {
     double b[3];
-    if constexpr (std::is_same<GM, GripField>::value) amg_rhs_row<GM>(op, code, dy_top, dy_bot, row, b, nullptr, g.d);
-    else amg_rhs_row<GM>(op, code, dy_top, dy_bot, row, b, &gp);
+    if constexpr (std::is_same<GM, GripField>::value)
+      amg_rhs_row<GM, LD>(op, code, dy_top, dy_bot, row, b, nullptr, g.d, ld);
+    else amg_rhs_row<GM, LD>(op, code, dy_top, dy_bot, row, b, &gp, nullptr, ld);
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       v.r[0][3 * row + a] = b[a];
@@ -2327,32 +2329,48 @@ void launch_amg_row0_inverse(hipStream_t s, const AmgCg& cg, int32_t* inv, int64
   hipLaunchKernelGGL(k_amg_row0_inverse, rows_grid(cg.hi - cg.lo), dim3(kBlock), 0, s, cg, inv);
 }
 
+// the grip form g and the load form ld chosen: the kernel by the lanes' DOFs
+template <class GM, class LD>
+static void amg_start_launch(hipStream_t s, int nd, const SellOp& op, const uint8_t* code, double dy_top,
+                             double dy_bot, const CgVecs& v, double* partials, unsigned* ticket, double* red_out,
+                             const AmgLevD& L0, const AmgCg& cg, const int32_t* inv, double rtol, double atol,
+                             int norm, int max_it, double reg, SolveState* st, double* zero, int64_t nzero, GM g,
+                             LD ld) {
+  const dim3 grid((unsigned)grid_rows(op.N > 0 ? op.N : 1));  // k_amg_rhs's (launch_cg_rhs)
+  if (nd == 2)
+    hipLaunchKernelGGL((k_amg_start<2, GM, LD>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials,
+                       ticket, red_out, L0, cg, inv, rtol, atol, norm, max_it, reg, st, zero, nzero, g, ld);
+  else
+    hipLaunchKernelGGL((k_amg_start<3, GM, LD>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials,
+                       ticket, red_out, L0, cg, inv, rtol, atol, norm, max_it, reg, st, zero, nzero, g, ld);
+}
+template <class LD>
+static void amg_start_grip(hipStream_t s, int nd, const SellOp& op, const uint8_t* code, double dy_top,
+                           double dy_bot, const CgVecs& v, double* partials, unsigned* ticket, double* red_out,
+                           const AmgLevD& L0, const AmgCg& cg, const int32_t* inv, double rtol, double atol,
+                           int norm, int max_it, double reg, SolveState* st, double* zero, int64_t nzero,
+                           const GripVec* grip, const double* field, LD ld) {
+  if (field)
+    amg_start_launch(s, nd, op, code, dy_top, dy_bot, v, partials, ticket, red_out, L0, cg, inv, rtol, atol, norm,
+                     max_it, reg, st, zero, nzero, GripField{field}, ld);
+  else if (grip)
+    amg_start_launch(s, nd, op, code, dy_top, dy_bot, v, partials, ticket, red_out, L0, cg, inv, rtol, atol, norm,
+                     max_it, reg, st, zero, nzero, *grip, ld);
+  else
+    amg_start_launch(s, nd, op, code, dy_top, dy_bot, v, partials, ticket, red_out, L0, cg, inv, rtol, atol, norm,
+                     max_it, reg, st, zero, nzero, GripY{}, ld);
+}
 void launch_amg_start(hipStream_t s, int nd, const SellOp& op, const uint8_t* code, double dy_top, double dy_bot,
                       const CgVecs& v, double* partials, unsigned* ticket, double* red_out, const AmgLevD& L0,
                       const AmgCg& cg, const int32_t* inv, double rtol, double atol, int norm, int max_it,
                       double reg, SolveState* st, double* zero, int64_t nzero, const GripVec* grip,
-                      const double* field) {
-  const dim3 grid((unsigned)grid_rows(op.N > 0 ? op.N : 1));  // k_amg_rhs's (launch_cg_rhs)
-  if (field && nd == 2)
-    hipLaunchKernelGGL((k_amg_start<2, GripField>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials,
-                       ticket, red_out, L0, cg, inv, rtol, atol, norm, max_it, reg, st, zero, nzero,
-                       GripField{field});
-  else if (field)
-    hipLaunchKernelGGL((k_amg_start<3, GripField>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials,
-                       ticket, red_out, L0, cg, inv, rtol, atol, norm, max_it, reg, st, zero, nzero,
-                       GripField{field});
-  else if (grip && nd == 2)
-    hipLaunchKernelGGL((k_amg_start<2, GripVec>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials,
-                       ticket, red_out, L0, cg, inv, rtol, atol, norm, max_it, reg, st, zero, nzero, *grip);
-  else if (grip)
-    hipLaunchKernelGGL((k_amg_start<3, GripVec>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials,
-                       ticket, red_out, L0, cg, inv, rtol, atol, norm, max_it, reg, st, zero, nzero, *grip);
-  else if (nd == 2)
-    hipLaunchKernelGGL((k_amg_start<2, GripY>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials,
-                       ticket, red_out, L0, cg, inv, rtol, atol, norm, max_it, reg, st, zero, nzero, GripY{});
+                      const double* field, const NodeLoad* load) {
+  if (load)
+    amg_start_grip(s, nd, op, code, dy_top, dy_bot, v, partials, ticket, red_out, L0, cg, inv, rtol, atol, norm,
+                   max_it, reg, st, zero, nzero, grip, field, *load);
   else
-    hipLaunchKernelGGL((k_amg_start<3, GripY>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials,
-                       ticket, red_out, L0, cg, inv, rtol, atol, norm, max_it, reg, st, zero, nzero, GripY{});
+    amg_start_grip(s, nd, op, code, dy_top, dy_bot, v, partials, ticket, red_out, L0, cg, inv, rtol, atol, norm,
+                   max_it, reg, st, zero, nzero, grip, field, LoadNone{});
 }
 
 template <int ND, int BS>

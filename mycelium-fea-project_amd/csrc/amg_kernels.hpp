@@ -342,7 +342,7 @@ void launch_amg_start(hipStream_t s, int nd, const SellOp& op, const uint8_t* co
                       const CgVecs& v, double* partials, unsigned* ticket, double* red_out, const AmgLevD& L0,
                       const AmgCg& cg, const int32_t* inv, double rtol, double atol, int norm, int max_it,
                       double reg, SolveState* st, double* zero, int64_t nzero, const GripVec* grip = nullptr,
-                      const double* field = nullptr);
+                      const double* field = nullptr, const NodeLoad* load = nullptr);
 // block partials of ‖r‖² alone, bitwise the next w launch's (component 2 of
 // cpart = [4][kCgMaxPartials]): the closing check of a chunk, launch_cg_advance
 void launch_amg_rnorm(hipStream_t s, int nd, const AmgCg& cg, double* cpart);

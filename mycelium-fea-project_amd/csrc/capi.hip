@@ -131,6 +131,15 @@ struct Part {
   // (kernels.hpp GripField; at least 3 doubles), uploaded by the setter and at
   // each build; mfea_get_grip_work's outputs (sums[0..2] of a band, the value)
   DevBuf<double> grip_d, gw_red;
+  // mfea_set_node_loads: the loads of the free rows in row order (kernels.hpp
+  // NodeLoad; at least 3 doubles), uploaded by the setter and at each build;
+  // the floating mask of the free rows in row order (launch_floating, label
+  // NULL) with the act_gen it reflects (−1: none yet) — recomputed only while
+  // loads are set; the form the kernels take; mfea_get_load_work's output
+  DevBuf<double> ld_f, lw_red;
+  DevBuf<uint8_t> ld_mask;
+  int64_t ld_mask_gen = -1;
+  NodeLoad ld{};
   // wave-local lane operator (ell.hip); ell_ok = false → SELL kernel
   Ell L;
   bool ell_ok = false;
@@ -308,6 +317,17 @@ struct mfea_handle : Options {
     if (!has_field) return grip.top[2] != 0.0 || grip.bot[2] != 0.0;
     for (size_t n = 2; n < field.size(); n += 3)
       if (field[n] != 0.0) return true;
+    return false;
+  }
+  // mfea_set_node_loads (one partition): a force vector per node, original
+  // node order, host copy; the mode; dy_top of the last solve (mfea_get_load_work)
+  std::vector<double> loads;
+  bool has_loads = false;
+  int32_t load_mode = MFEA_LOAD_DEAD;
+  double load_dy_top = 0.0;
+  bool load_z() const {
+    for (size_t n = 2; n < loads.size(); n += 3)
+      if (loads[n] != 0.0) return true;
     return false;
   }
   // host-side mesh/BC (original order)
@@ -616,6 +636,49 @@ int upload_field(mfea_handle* h, Part& pt) {
 // the kernels' `field` argument: null without a grip field
 const double* field_arg(const mfea_handle* h, const Part& pt) { return h->has_field ? pt.grip_d.ptr : nullptr; }
 
+// The nodal loads of the free rows, gathered into Pattern row order and
+// uploaded; waited for, before and after.  The floating mask of this build
+// starts as zeros and counts as not computed (ensure_load_mask); it depends on
+// the activity alone, so other loads on the same build keep it.
+int upload_loads(mfea_handle* h, Part& pt) {
+  const Pattern& P = pt.P;
+  std::vector<double> rows((size_t)3 * std::max<int64_t>(P.n_free, 1), 0.0);
+  for (int64_t r = 0; r < P.n_free; ++r)
+    for (int c = 0; c < 3; ++c) rows[3 * r + c] = h->loads[3 * (size_t)P.perm[r] + c];
+  HIPC(hipStreamSynchronize(h->stream));
+  HIPC(pt.ld_f.alloc(rows.size()));
+  HIPC(hmemcpy(h, pt.ld_f.ptr, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice));
+  if (!pt.ld_mask.ptr) {
+    HIPC(pt.ld_mask.alloc(std::max<int64_t>(P.n_free, 1)));
+    HIPC(hmemset(h, pt.ld_mask.ptr, 0, std::max<int64_t>(P.n_free, 1)));
+    pt.ld_mask_gen = -1;
+  }
+  pt.ld = NodeLoad{pt.ld_f.ptr, pt.ld_mask.ptr, h->load_mode == MFEA_LOAD_PROPORTIONAL ? 1 : 0};
+  return 0;
+}
+// the kernels' `load` argument: null without loads
+const NodeLoad* load_arg(const mfea_handle* h, const Part& pt) { return h->has_loads ? &pt.ld : nullptr; }
+
+// The floating mask the load kernels read, of the device's current activity:
+// recomputed (launch_floating in row order, four launches on the stream, no
+// wait) when the activity has moved since it was formed — only while loads
+// are set.  Called in front of every assembly and step, outside any capture,
+// so the mask is that of the activity the step's K is assembled from.
+int ensure_load_mask(mfea_handle* h) {
+  if (!h->has_loads || h->parts.size() != 1) return 0;
+  Part& pt = *h->parts[0];
+  const Pattern& P = pt.P;
+  if (pt.ld_mask_gen == h->act_gen || P.n_free == 0) return 0;
+  HIPC(pt.cc_parent.alloc(std::max<int64_t>(P.n_nodes, 1)));
+  HIPC(pt.cc_anch.alloc(std::max<int64_t>(P.n_nodes, 1)));
+  launch_floating(h->stream, P.n_nodes, P.n_free, P.n_nodes - P.n_ghost, pt.slice_ptr.ptr, pt.row_len.ptr,
+                  pt.s_col.ptr, pt.s_elem.ptr, pt.active.ptr, pt.cc_parent.ptr, pt.cc_anch.ptr, nullptr,
+                  pt.ld_mask.ptr, h->opt_cc_tile);
+  HIPC(hipGetLastError());
+  pt.ld_mask_gen = h->act_gen;
+  return 0;
+}
+
 double* cg_part_buf(Part& pt, int par) { return pt.cg_part.ptr + (size_t)par * 4 * kCgMaxPartials; }
 
 void destroy_graph(mfea_handle* h) {
@@ -654,8 +717,11 @@ int order_mode(const mfea_handle* h) { return h->opt_order; }
 // planar meshes run with 2 DOFs per node (option "lane_dof" 3 forces 3, and
 // so does a grip motion with a z component: the solution leaves the plane);
 // decided on the whole mesh so every partition exchanges records of one width
-// (grip_z: of the field's rows while a grip field is set)
-int lane_dofs(const mfea_handle* h) { return (h->planar && h->opt_lane_dof != 3 && !h->grip_z()) ? 2 : 3; }
+// (grip_z: of the field's rows while a grip field is set; load_z: a nodal load
+// with a z entry takes the solution out of the plane as well)
+int lane_dofs(const mfea_handle* h) {
+  return (h->planar && h->opt_lane_dof != 3 && !h->grip_z() && !h->load_z()) ? 2 : 3;
+}
 
 // Waits for an event.  Partitioned over RCCL: polls with a deadline and the
 // communicator's error state, so a lost peer ends the call instead of hanging.
@@ -856,6 +922,8 @@ int ensure_built(mfea_handle* h) {
     return fail(MFEA_ESTATE, "per-element properties: one partition per handle (mfea_set_element_props(h, NULL) first)");
   if (dm && h->has_field)
     return fail(MFEA_ESTATE, "grip field: one partition per handle (mfea_set_grip_field(h, NULL) first)");
+  if (dm && h->has_loads)
+    return fail(MFEA_ESTATE, "nodal loads: one partition per handle (mfea_set_node_loads(h, NULL, 0) first)");
   if (dm && !h->grip_default())
     return fail(MFEA_ESTATE, "grip motion: one partition per handle (set the directions (0,1,0), (0,1,0) first)");
   const int np = h->world > 1 ? 1 : h->nparts;
@@ -889,6 +957,7 @@ int ensure_built(mfea_handle* h) {
     }
     RC(upload_part(h, pt, dm));
     if (h->has_field) RC(upload_field(h, pt));
+    if (h->has_loads) RC(upload_loads(h, pt));
   }
   if (dm) {  // distributed GAMG: the whole mesh's pattern and the node owners
     h->gamg_ok = false;
@@ -1391,7 +1460,7 @@ int solve_impl(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_op
   const CgVecs v = cg_vecs(pt);
   RC(phase_event(h, h->ev[1], s));
   launch_cg_rhs(s, op, pt.code.ptr, dy_top, dy_bot, o->reg, precond, v, pt.partials.ptr, tix(pt, 0),
-                pt.red.ptr, h->grip_arg(), field_arg(h, pt));
+                pt.red.ptr, h->grip_arg(), field_arg(h, pt), load_arg(h, pt));
   launch_cg_init_finalize(s, pt.red.ptr, o->rtol, o->atol, o->norm, o->max_it, o->reg,
                           pt.state.ptr,
                           pt.cg_part.ptr, 2 * 4 * kCgMaxPartials);
@@ -2398,6 +2467,7 @@ void enqueue_step_head(mfea_handle* h, Part& pt, const mfea_solve_opts* o) {
   q.grip = h->grip;
   q.vec = !h->grip_default();
   q.field = field_arg(h, pt);
+  if (h->has_loads) q.load = pt.ld;
   q.nf = P.n_free;
   q.r = pt.r.ptr;
   q.x = pt.x.ptr;
@@ -2606,12 +2676,12 @@ int solve_amg(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opt
       launch_amg_start(s, nd, op, pt.code.ptr, dy_top, dy_bot, v, pt.partials.ptr, tix(pt, 0), pt.red.ptr,
                        pt.amg_lev[0], pt.amg_cg, pt.amg_inv.ptr, o->rtol, o->atol, o->norm, o->max_it, o->reg,
                        pt.state.ptr, pt.cg_part.ptr, 2 * 4 * kCgMaxPartials, h->grip_arg(),
-                       field_arg(h, pt));
+                       field_arg(h, pt), load_arg(h, pt));
       ++h->amg_start_fused;
     } else {
       if (!rhs_done)
         launch_cg_rhs(s, op, pt.code.ptr, dy_top, dy_bot, o->reg, 2, v, pt.partials.ptr, tix(pt, 0), pt.red.ptr,
-                      h->grip_arg(), field_arg(h, pt));
+                      h->grip_arg(), field_arg(h, pt), load_arg(h, pt));
       if (!start_in_graph)
         launch_cg_init_finalize(s, pt.red.ptr, o->rtol, o->atol, o->norm, o->max_it, o->reg, pt.state.ptr,
                                 pt.cg_part.ptr, 2 * 4 * kCgMaxPartials);
@@ -3541,6 +3611,7 @@ bool ensure_colour(mfea_handle* h, Part& pt) {
 
 int assemble_impl(mfea_handle* h, mfea_stats* st, const double* rhs_dy = nullptr) {
   hipStream_t s = h->stream;
+  RC(ensure_load_mask(h));  // (a no-op inside a step: step_impl has called it)
   h->assembled = true;
   h->rhs_fused = false;
   k_written(h);
@@ -3569,6 +3640,7 @@ int assemble_impl(mfea_handle* h, mfea_stats* st, const double* rhs_dy = nullptr
       q.grip = h->grip;
       q.vec = !h->grip_default();
       q.field = field_arg(h, pt);
+      if (h->has_loads) q.load = pt.ld;
       q.nf = P.n_free;
       q.r = pt.r.ptr;
       q.x = pt.x.ptr;
@@ -3916,6 +3988,7 @@ int solve_any(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opt
               mfea_stats* st) {
   h->ev_setup_used = false;
   h->setup_skipped = false;
+  h->load_dy_top = dy_top;  // (mfea_get_load_work: the amplitude of the last solve)
   // another preconditioner kind than the last solve's: its setup runs
   if (o->precond != h->last_precond) drop_kept_setup(h);
   h->last_precond = o->precond;
@@ -4213,6 +4286,71 @@ int mfea_get_grip_work(mfea_handle* h, double* top, double* bot) {
   return 0;
 }
 
+// A force vector per free node (kernels.hpp NodeLoad): it enters where the
+// grips' values enter, the five RHS sites, and a change drops what a change of
+// them drops (grip_changed).  The host copy is the state; the device rows are
+// gathered from it here, when the handle is built, and at every build.
+int mfea_set_node_loads(mfea_handle* h, const double* loads, int32_t mode) {
+  if (!h) return fail(MFEA_EINVAL, "NULL handle");
+  if (!h->has_mesh) return fail(MFEA_ESTATE, "set the mesh before the nodal loads");
+  if (h->world > 1 || h->nparts > 1) return fail(MFEA_ESTATE, "mfea_set_node_loads: one partition per handle");
+  if (loads && mode != MFEA_LOAD_DEAD && mode != MFEA_LOAD_PROPORTIONAL)
+    return fail(MFEA_EINVAL, "mfea_set_node_loads: mode must be MFEA_LOAD_DEAD or MFEA_LOAD_PROPORTIONAL");
+  const size_t n = (size_t)3 * h->N;
+  std::vector<double> f;
+  if (loads) {
+    f.resize(n);
+    for (size_t k = 0; k < n; ++k) {
+      if (!std::isfinite(loads[k])) return fail(MFEA_EINVAL, "mfea_set_node_loads: every entry must be finite");
+      f[k] = loads[k] + 0.0;  // (a −0 entry is stored as 0)
+    }
+  }
+  if (h->has_loads == (loads != nullptr) &&
+      (!loads || (h->load_mode == mode && (n == 0 || std::memcmp(f.data(), h->loads.data(), n * sizeof(double)) == 0))))
+    return 0;
+  RC(set_device(h));
+  const int nd0 = lane_dofs(h);
+  if (h->stream) HIPC(hipStreamSynchronize(h->stream));
+  h->loads.swap(f);
+  h->has_loads = loads != nullptr;
+  h->load_mode = loads ? mode : MFEA_LOAD_DEAD;
+  RC(grip_changed(h, nd0));
+  if (h->has_loads && !h->dirty && h->parts.size() == 1) RC(upload_loads(h, part0(h)));
+  return 0;
+}
+
+int mfea_get_node_loads(mfea_handle* h, double* loads, int32_t* mode, int32_t* is_set) {
+  if (!h) return fail(MFEA_EINVAL, "NULL handle");
+  if (!h->has_mesh) return fail(MFEA_ESTATE, "no mesh: call mfea_set_mesh first");
+  if (is_set) *is_set = h->has_loads ? 1 : 0;
+  if (mode) *mode = h->load_mode;
+  if (!loads) return 0;
+  if (h->has_loads) std::copy(h->loads.begin(), h->loads.end(), loads);
+  else std::fill(loads, loads + 3 * h->N, 0.0);
+  return 0;
+}
+
+// L = Σ q·u over the free, non-floating rows (kernels.hip k_load_work): the
+// amplitude and the mask of the last solve, the current U; states as
+// mfea_get_reaction.  The post's partials and ticket set, behind the post on
+// the stream; the output in a buffer of the call's own.
+int mfea_get_load_work(mfea_handle* h, double* work) {
+  if (!h || !work) return fail(MFEA_EINVAL, "NULL argument");
+  RC(set_device(h));
+  RC(ensure_built(h));
+  if (partitioned(h)) return fail(MFEA_ESTATE, "mfea_get_load_work: one partition per handle");
+  if (!h->assembled) return fail(MFEA_ESTATE, "mfea_get_load_work: no assembly since the last build");
+  *work = 0.0;
+  if (!h->has_loads) return 0;
+  Part& pt = part0(h);
+  HIPC(pt.lw_red.alloc(1));
+  launch_load_work(h->stream, pt.P.n_free, pt.ld, h->load_dy_top, pt.x.ptr, pt.partials.ptr, tix(pt, 3),
+                   pt.lw_red.ptr);
+  HIPC(hipGetLastError());
+  HIPC(hmemcpy(h, work, pt.lw_red.ptr, sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
 // The strain energy of every element that counts and its two parts per unit
 // section (kernels.hip k_energy), on the handle's stream: behind everything
 // earlier calls enqueued there — a speculative post's undo included — so the
@@ -4349,6 +4487,13 @@ int mfea_set_mesh(mfea_handle* h, int64_t n_nodes, const double* xyz, int64_t n_
   h->act_all = false;
   h->active_host.clear();
   clear_props(h);  // (indexed by the old mesh's elements)
+  if (h->has_loads) {  // (... the nodal loads by its nodes: cleared, as mfea_set_node_loads(h, NULL, 0))
+    if (h->stream) HIPC(hipStreamSynchronize(h->stream));
+    h->loads.clear();
+    h->has_loads = false;
+    h->load_mode = MFEA_LOAD_DEAD;
+    RC(grip_changed(h, lane_dofs(h)));
+  }
   if (h->has_field) {  // (... the grip field by its nodes: cleared, as mfea_set_grip_field(h, NULL))
     if (h->stream) HIPC(hipStreamSynchronize(h->stream));
     h->field.clear();
@@ -4445,6 +4590,9 @@ int mfea_solve(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_op
   // a (re)build (new mesh / BCs, a layout option) left the operator empty:
   // assemble the current active set first rather than solve a zero operator
   if (!h->assembled) RC(assemble_impl(h, nullptr));
+  // (nodal loads set after the assembly: no mask of K's activity yet — the
+  // current one's, which is K's unless a post has moved it since)
+  if (h->has_loads && !partitioned(h) && part0(h).ld_mask_gen != h->k_from.act_gen) RC(ensure_load_mask(h));
   return solve_any(h, dy_top, dy_bot, &o, st);
 }
 
@@ -4460,6 +4608,9 @@ static int step_impl(mfea_handle* h, double dy_top, double dy_bot, const mfea_so
                      double max_strain, double* total_force, int64_t* n_active, mfea_stats* st) {
   mfea_solve_opts o = opts ? *opts : default_opts();
   if (st) std::memset(st, 0, sizeof(*st));
+  // nodal loads: the floating mask of the activity this step's K is assembled
+  // from, in front of every RHS of the step and outside its graphs
+  RC(ensure_load_mask(h));
   // the one-partition GAMG / SOR / ICC solves take their RHS from the
   // assembly's row pass (AsmRhs)
   const bool fuse_rhs = !partitioned(h) && (o.precond == MFEA_PC_GAMG || o.precond == MFEA_PC_SOR ||
@@ -4483,7 +4634,7 @@ static int step_impl(mfea_handle* h, double dy_top, double dy_bot, const mfea_so
     if (fuse_rhs && !(h->opt_amg_start && o.precond == MFEA_PC_GAMG)) {
       Part& pt = part0(h);
       launch_cg_rhs(s, sell_op(pt), pt.code.ptr, dy_top, dy_bot, o.reg, 2, cg_vecs(pt), pt.partials.ptr, tix(pt, 0),
-                    pt.red.ptr, h->grip_arg(), field_arg(h, pt));
+                    pt.red.ptr, h->grip_arg(), field_arg(h, pt), load_arg(h, pt));
       HIPC(hipGetLastError());
       h->rhs_fused = true;
       h->rhs_dy[0] = dy_top;
@@ -4542,6 +4693,11 @@ int mfea_step(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opt
 // ---------------------------------------------------------------------------
 // mfea_event: one step at the reference load whose post is the event pair.
 // ---------------------------------------------------------------------------
+// events scale one solve to each failure load: U must be proportional to the
+// amplitudes, which a dead load breaks (the response is affine in the factor)
+static const char kDeadLoadEvents[] =
+    "events need a response proportional to the amplitudes: dead nodal loads make it affine in the load factor "
+    "(mfea_set_node_loads with MFEA_LOAD_PROPORTIONAL, or NULL, first)";
 static int event_check(const mfea_event_opts* ev) {
   if (!ev) return fail(MFEA_EINVAL, "NULL argument");
   if (!(ev->max_strain > 0.0)) return fail(MFEA_EINVAL, "mfea_event: max_strain must be > 0");
@@ -4593,6 +4749,7 @@ int mfea_event(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_op
   RC(set_device(h));
   RC(ensure_built(h));
   if (partitioned(h)) return fail(MFEA_ESTATE, "mfea_event: one partition per handle");
+  if (h->has_loads && h->load_mode == MFEA_LOAD_DEAD) return fail(MFEA_ESTATE, kDeadLoadEvents);
   return event_impl(h, dy_top, dy_bot, opts, evopts, 0, out, st);
 }
 
@@ -4882,6 +5039,7 @@ int mfea_run_events(mfea_handle* h, int32_t n_events, double dy_top, double dy_b
   RC(set_device(h));
   RC(ensure_built(h));
   if (partitioned(h)) return fail(MFEA_ESTATE, "mfea_run_events: one partition per handle");
+  if (h->has_loads && h->load_mode == MFEA_LOAD_DEAD) return fail(MFEA_ESTATE, kDeadLoadEvents);
   Part& pt = part0(h);
   const int64_t E = pt.P.n_elems;
   if (E) HIPC(hipMemsetAsync(pt.event_of.ptr, 0xFF, E * sizeof(int32_t), h->stream));

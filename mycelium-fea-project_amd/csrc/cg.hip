@@ -69,12 +69,14 @@ __device__ __forceinline__ void store3(double* __restrict__ v, int64_t row, cons
 // GM = GripVec (kernels.hpp): known rows x = p = fl(dy · direction), and a
 // known neighbour's whole block, b −= V p (grip_mac).
 // GM = GripField: the same with p per known row, fl(dy of its class · its vector).
+// LD = NodeLoad (kernels.hpp): b = q − K_fk x_k, the row's load and mask byte
+// fetched with its slot pointer and length.
 // ---------------------------------------------------------------------------
-template <bool BLOCK, class GM>
+template <bool BLOCK, class GM, class LD = LoadNone>
 __global__ __launch_bounds__(kBlock) void k_cg_rhs(SellOp op, const uint8_t* __restrict__ code,
                                                    double dy_top, double dy_bot, double reg,
                                                    CgVecs v, double* partials, unsigned* ticket,
-                                                   double* red_out, GM g) {
+                                                   double* red_out, GM g, LD ld) {
   const int64_t row = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   double acc[2] = {0.0, 0.0};  // b·b, u₀·u₀
   const double zero[3] = {0.0, 0.0, 0.0};
@@ -85,6 +87,7 @@ __global__ __launch_bounds__(kBlock) void k_cg_rhs(SellOp op, const uint8_t* __r
   if (row < op.nf) {
     const int64_t base = (int64_t)op.slice_ptr[row >> 6] * 64 + (row & 63);
     const int len = op.row_len[row];
+    const LoadRow<LD> lr = load_fetch(ld, row);
     const int64_t G = op.G;
     double kx = 0.0, ky = 0.0, kz = 0.0;
     for (int k = 0; k < len; ++k) {
@@ -117,7 +120,9 @@ __global__ __launch_bounds__(kBlock) void k_cg_rhs(SellOp op, const uint8_t* __r
         }
       }
     }
-    const double b[3] = {0.0 - kx, 0.0 - ky, 0.0 - kz};
+    const double kf[3] = {kx, ky, kz};
+    double b[3];
+    load_rhs(ld, lr, dy_top, kf, b);
     double A[6];
 #pragma unroll
     for (int c = 0; c < 6; ++c) A[c] = op.diag[(int64_t)c * op.N + row];
@@ -175,10 +180,11 @@ __global__ __launch_bounds__(kBlock) void k_cg_rhs(SellOp op, const uint8_t* __r
 // (GAMG stops on the unpreconditioned residual).  A row's slots in batches of
 // four: columns, then their codes, then the known couplings.  b's terms in
 // slot order, as k_cg_rhs.
-template <class GM>
+template <class GM, class LD = LoadNone>
 __global__ __launch_bounds__(kBlock) void k_amg_rhs(SellOp op, const uint8_t* __restrict__ code,
                                                     double dy_top, double dy_bot, CgVecs v,
-                                                    double* partials, unsigned* ticket, double* red_out, GM g) {
+                                                    double* partials, unsigned* ticket, double* red_out, GM g,
+                                                    LD ld) {
   const int64_t row = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   double acc[2] = {0.0, 0.0};
   constexpr bool VEC = std::is_same<GM, GripVec>::value;
@@ -186,8 +192,9 @@ __global__ __launch_bounds__(kBlock) void k_amg_rhs(SellOp op, const uint8_t* __
   if constexpr (VEC) gp = grip_disp(g, dy_top, dy_bot);
   if (row < op.nf) {
     double b[3];
-    if constexpr (std::is_same<GM, GripField>::value) amg_rhs_row<GM>(op, code, dy_top, dy_bot, row, b, nullptr, g.d);
-    else amg_rhs_row<GM>(op, code, dy_top, dy_bot, row, b, &gp);
+    if constexpr (std::is_same<GM, GripField>::value)
+      amg_rhs_row<GM, LD>(op, code, dy_top, dy_bot, row, b, nullptr, g.d, ld);
+    else amg_rhs_row<GM, LD>(op, code, dy_top, dy_bot, row, b, &gp, nullptr, ld);
     store3(v.r[0], row, b);
 #pragma unroll
     for (int a = 0; a < 3; ++a) acc[0] = fma(b[a], b[a], acc[0]);
@@ -509,44 +516,41 @@ __global__ void k_cg_advance(int chunk, int shift, Slot* slots, SolveState* st, 
 }
 
 // ---------------------------------------------------------------------------
+// the grip form g and the load form ld chosen: the kernel by the preconditioner
+template <class GM, class LD>
+static void cg_rhs_launch(hipStream_t s, const SellOp& op, const uint8_t* code, double dy_top, double dy_bot,
+                          double reg, int precond, const CgVecs& v, double* partials, unsigned* ticket,
+                          double* red_out, GM g, LD ld) {
+  const dim3 grid((unsigned)grid_rows(op.N > 0 ? op.N : 1));
+  if (precond == 2)
+    hipLaunchKernelGGL((k_amg_rhs<GM, LD>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials, ticket,
+                       red_out, g, ld);
+  else if (precond == 1)
+    hipLaunchKernelGGL((k_cg_rhs<true, GM, LD>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, reg, v,
+                       partials, ticket, red_out, g, ld);
+  else
+    hipLaunchKernelGGL((k_cg_rhs<false, GM, LD>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, reg, v,
+                       partials, ticket, red_out, g, ld);
+}
+template <class LD>
+static void cg_rhs_grip(hipStream_t s, const SellOp& op, const uint8_t* code, double dy_top, double dy_bot,
+                        double reg, int precond, const CgVecs& v, double* partials, unsigned* ticket,
+                        double* red_out, const GripVec* grip, const double* field, LD ld) {
+  if (field)  // (a grip field: before the directions)
+    cg_rhs_launch(s, op, code, dy_top, dy_bot, reg, precond, v, partials, ticket, red_out, GripField{field}, ld);
+  else if (grip)  // (the directions other than the tensile test's)
+    cg_rhs_launch(s, op, code, dy_top, dy_bot, reg, precond, v, partials, ticket, red_out, *grip, ld);
+  else
+    cg_rhs_launch(s, op, code, dy_top, dy_bot, reg, precond, v, partials, ticket, red_out, GripY{}, ld);
+}
 void launch_cg_rhs(hipStream_t s, const SellOp& op, const uint8_t* code, double dy_top,
                    double dy_bot, double reg, int precond, const CgVecs& v, double* partials,
-                   unsigned* ticket, double* red_out, const GripVec* grip, const double* field) {
-  const dim3 grid((unsigned)grid_rows(op.N > 0 ? op.N : 1));
-  if (field) {  // (a grip field: before the directions)
-    const GripField f{field};
-    if (precond == 2)
-      hipLaunchKernelGGL(k_amg_rhs<GripField>, grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials, ticket,
-                         red_out, f);
-    else if (precond == 1)
-      hipLaunchKernelGGL((k_cg_rhs<true, GripField>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, reg, v,
-                         partials, ticket, red_out, f);
-    else
-      hipLaunchKernelGGL((k_cg_rhs<false, GripField>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, reg, v,
-                         partials, ticket, red_out, f);
-    return;
-  }
-  if (grip) {  // (the directions other than the tensile test's)
-    if (precond == 2)
-      hipLaunchKernelGGL(k_amg_rhs<GripVec>, grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials, ticket,
-                         red_out, *grip);
-    else if (precond == 1)
-      hipLaunchKernelGGL((k_cg_rhs<true, GripVec>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, reg, v,
-                         partials, ticket, red_out, *grip);
-    else
-      hipLaunchKernelGGL((k_cg_rhs<false, GripVec>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, reg, v,
-                         partials, ticket, red_out, *grip);
-    return;
-  }
-  if (precond == 2)
-    hipLaunchKernelGGL(k_amg_rhs<GripY>, grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials, ticket,
-                       red_out, GripY{});
-  else if (precond == 1)
-    hipLaunchKernelGGL((k_cg_rhs<true, GripY>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, reg, v,
-                       partials, ticket, red_out, GripY{});
+                   unsigned* ticket, double* red_out, const GripVec* grip, const double* field,
+                   const NodeLoad* load) {
+  if (load)
+    cg_rhs_grip(s, op, code, dy_top, dy_bot, reg, precond, v, partials, ticket, red_out, grip, field, *load);
   else
-    hipLaunchKernelGGL((k_cg_rhs<false, GripY>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, reg, v,
-                       partials, ticket, red_out, GripY{});
+    cg_rhs_grip(s, op, code, dy_top, dy_bot, reg, precond, v, partials, ticket, red_out, grip, field, LoadNone{});
 }
 
 void launch_cg_init_finalize(hipStream_t s, const double* red, double rtol, double atol, int norm,

@@ -300,6 +300,46 @@ __device__ __forceinline__ void grip_mac(const double v[6], const double p[3], d
   k[2] = fma(v[5], p[2], fma(v[4], p[1], fma(v[2], p[0], k[2])));
 }
 
+// Nodal loads (kernels.hpp NodeLoad): a free row's three stored doubles and its
+// mask byte, fetched where the row's first loads are issued (the slot pointer
+// and the row length), not behind the slot loop — nothing else depends on them
+// before the loop ends.  LoadNone: nothing is loaded and b = 0 − k.
+template <class LD>
+struct LoadRow {};
+template <>
+struct LoadRow<NodeLoad> {
+  double f[3];
+  uint8_t fl;
+};
+__device__ __forceinline__ LoadRow<LoadNone> load_fetch(const LoadNone&, int64_t) { return {}; }
+__device__ __forceinline__ LoadRow<NodeLoad> load_fetch(const NodeLoad& ld, int64_t row) {
+  LoadRow<NodeLoad> r;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) r.f[c] = ld.f[3 * row + c];
+  r.fl = ld.fl[row];
+  return r;
+}
+// q of the row: one product per component (amp 1 for a dead load), 0 on a
+// floating row; + 0 turns a product −0 into 0
+__device__ __forceinline__ void load_q(const NodeLoad& ld, const LoadRow<NodeLoad>& lr, double dy_top, double q[3]) {
+  const double amp = ld.prop ? dy_top : 1.0;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) q[c] = lr.fl ? 0.0 : amp * lr.f[c] + 0.0;
+}
+// b = q − k (LoadNone: 0 − k), one subtraction per component
+__device__ __forceinline__ void load_rhs(const LoadNone&, const LoadRow<LoadNone>&, double, const double k[3],
+                                         double b[3]) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) b[c] = 0.0 - k[c];
+}
+__device__ __forceinline__ void load_rhs(const NodeLoad& ld, const LoadRow<NodeLoad>& lr, double dy_top,
+                                         const double k[3], double b[3]) {
+  double q[3];
+  load_q(ld, lr, dy_top, q);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) b[c] = q[c] - k[c];
+}
+
 // b = 0 − K_fk x_k of free row `row` for the GAMG solves (k_amg_rhs, cg.hip;
 // k_amg_start, amg.hip).  A row's slots in batches of four: columns, then
 // their codes, then the known couplings; b's terms in slot order.
@@ -308,12 +348,14 @@ __device__ __forceinline__ void grip_mac(const double v[6], const double p[3], d
 // vectors of a batch's four neighbours loaded together after the codes, every
 // load unconditional on an index clamped into the known rows, the class applied
 // after (a guarded load would serialise the batch).
-template <class GM = GripY>
+// LD = NodeLoad (ld): b = q − k, the row's load fetched with its first loads.
+template <class GM = GripY, class LD = LoadNone>
 __device__ __forceinline__ void amg_rhs_row(const SellOp& op, const uint8_t* __restrict__ code, double dy_top,
                                             double dy_bot, int64_t row, double b[3], const GripP* p = nullptr,
-                                            const double* __restrict__ fd = nullptr) {
+                                            const double* __restrict__ fd = nullptr, const LD& ld = LD{}) {
   const int64_t base = (int64_t)op.slice_ptr[row >> 6] * 64 + (row & 63);
   const int len = op.row_len[row];
+  const LoadRow<LD> lr = load_fetch(ld, row);
   const int64_t G = op.G;
   double kx = 0.0, ky = 0.0, kz = 0.0;
   if constexpr (std::is_same<GM, GripField>::value) {
@@ -348,9 +390,7 @@ __device__ __forceinline__ void amg_rhs_row(const SellOp& op, const uint8_t* __r
         }
       }
     }
-    b[0] = 0.0 - k3[0];
-    b[1] = 0.0 - k3[1];
-    b[2] = 0.0 - k3[2];
+    load_rhs(ld, lr, dy_top, k3, b);
     return;
   }
   if constexpr (std::is_same<GM, GripVec>::value) {
@@ -378,9 +418,7 @@ __device__ __forceinline__ void amg_rhs_row(const SellOp& op, const uint8_t* __r
         }
       }
     }
-    b[0] = 0.0 - k3[0];
-    b[1] = 0.0 - k3[1];
-    b[2] = 0.0 - k3[2];
+    load_rhs(ld, lr, dy_top, k3, b);
     return;
   }
   constexpr int U = 4;
@@ -405,9 +443,8 @@ __device__ __forceinline__ void amg_rhs_row(const SellOp& op, const uint8_t* __r
       }
     }
   }
-  b[0] = 0.0 - kx;
-  b[1] = 0.0 - ky;
-  b[2] = 0.0 - kz;
+  const double k3[3] = {kx, ky, kz};
+  load_rhs(ld, lr, dy_top, k3, b);
 }
 
 // The CG's state at the start of a solve, from the reduced (‖b‖², ‖M⁻¹b‖²)

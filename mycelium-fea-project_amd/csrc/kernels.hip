@@ -277,7 +277,10 @@ __global__ __launch_bounds__(kBlock) void k_diag_rows(int64_t N, const int32_t* 
 
 // RHS: the GAMG solves' RHS too (AsmRhs: k_amg_rhs's outputs from the −S_e
 // blocks in registers) — one launch fewer per step
-template <bool RHS, class M, class GM = GripY>
+// LD = NodeLoad (q.load): b = q − k; the row's load and mask byte are fetched
+// in front of the row pass, with its slot pointer, length and coordinates, on
+// the row clamped into the free rows (a known row reads row 0 and drops it).
+template <bool RHS, class M, class GM = GripY, class LD = LoadNone>
 __global__ __launch_bounds__(kBlock) void k_assemble(int64_t N, const double* __restrict__ xyz,
                                                      const int32_t* __restrict__ slice_ptr,
                                                      const int32_t* __restrict__ row_len,
@@ -298,9 +301,13 @@ __global__ __launch_bounds__(kBlock) void k_assemble(int64_t N, const double* __
     double acc[2] = {0.0, 0.0};
     if (row < N) {
       double k3[3] = {0.0, 0.0, 0.0};
+      LD ld{};
+      if constexpr (std::is_same<LD, NodeLoad>::value) ld = q.load;
+      const LoadRow<LD> lr = load_fetch(ld, row < q.nf ? row : 0);
       assemble_row<M, GM>(N, row, xyz, slice_ptr, row_len, s_col, s_elem, active, m, G, val, diag, &q, k3, &gp);
       if (row < q.nf) {
-        const double b[3] = {0.0 - k3[0], 0.0 - k3[1], 0.0 - k3[2]};
+        double b[3];
+        load_rhs(ld, lr, q.dy_top, k3, b);
 #pragma unroll
         for (int a = 0; a < 3; ++a) q.r[3 * row + a] = b[a];
 #pragma unroll
@@ -328,13 +335,14 @@ __global__ __launch_bounds__(kBlock) void k_assemble(int64_t N, const double* __
 // free-row SpMV sees K_fk·p = 0.  Reduces (r·z, b·b, z·z).
 // ---------------------------------------------------------------------------
 
-template <class GM>
+// LD = NodeLoad: b = q − K_fk x_k (kernels.hpp), fetched with the row's first loads
+template <class GM, class LD = LoadNone>
 __global__ __launch_bounds__(kBlock) void k_rhs_init(
     int64_t N, int64_t nf, const int32_t* __restrict__ slice_ptr, const int32_t* __restrict__ row_len,
     const int32_t* __restrict__ s_col, const double* __restrict__ val, const double* __restrict__ diag,
     int64_t G, const uint8_t* __restrict__ code, double dy_top, double dy_bot, double reg,
     int precond, double* __restrict__ x, double* __restrict__ r, double* __restrict__ p,
-    double* __restrict__ dinv, double* partials, unsigned* ticket, double* red_out, GM g) {
+    double* __restrict__ dinv, double* partials, unsigned* ticket, double* red_out, GM g, LD ld) {
   const int64_t row = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   double acc[3] = {0.0, 0.0, 0.0};  // r·z, b·b, z·z
   constexpr bool VEC = std::is_same<GM, GripVec>::value;
@@ -344,6 +352,7 @@ __global__ __launch_bounds__(kBlock) void k_rhs_init(
   if (row < nf) {
     const int64_t base = (int64_t)slice_ptr[row >> 6] * 64 + (row & 63);
     const int len = row_len[row];
+    const LoadRow<LD> lr = load_fetch(ld, row);
     double kx = 0.0, ky = 0.0, kz = 0.0;  // (K_fk · x_k) for this row
     for (int k = 0; k < len; ++k) {
       const int64_t idx = base + (int64_t)k * 64;
@@ -375,7 +384,9 @@ __global__ __launch_bounds__(kBlock) void k_rhs_init(
         }
       }
     }
-    const double b[3] = {0.0 - kx, 0.0 - ky, 0.0 - kz};  // F_f = 0 − K_fk x_k (py:122)
+    const double kf[3] = {kx, ky, kz};
+    double b[3];
+    load_rhs(ld, lr, dy_top, kf, b);  // F_f = 0 − K_fk x_k (py:122), or q − K_fk x_k
     double A[6];
 #pragma unroll
     for (int c = 0; c < 6; ++c) A[c] = diag[(int64_t)c * N + row];
@@ -676,6 +687,27 @@ __global__ __launch_bounds__(kBlock) void k_reaction(int64_t row0, int64_t nrows
     f[0] = fy;
   }
   block_publish<1>(f, partials, ticket, red_out);
+}
+
+// ---------------------------------------------------------------------------
+// The work of the nodal loads (mfea_get_load_work): one lane per free row,
+// L_r = (q[0]·u[0] + q[1]·u[1]) + q[2]·u[2] with q as the RHS kernels form it
+// (0 on a floating row), f64, nothing fused; k_reaction's publish, so the rows
+// reduce in its fixed order.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_load_work(int64_t nf, NodeLoad ld, double dy_top,
+                                                      const double* __restrict__ u, double* partials,
+                                                      unsigned* ticket, double* red_out) {
+  const int64_t row = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  double w[1] = {0.0};
+  if (row < nf) {
+    const LoadRow<NodeLoad> lr = load_fetch(ld, row);
+    const double ur[3] = {u[3 * row], u[3 * row + 1], u[3 * row + 2]};
+    double q[3];
+    load_q(ld, lr, dy_top, q);
+    w[0] = grip_work_row(q, ur);
+  }
+  block_publish<1>(w, partials, ticket, red_out);
 }
 
 // ---------------------------------------------------------------------------
@@ -1014,30 +1046,42 @@ __global__ __launch_bounds__(kBlock) void k_spmv_csr(int j, int64_t n, const int
 // ---------------------------------------------------------------------------
 #define MFEA_GRID(n) dim3((unsigned)(n)), dim3(kBlock), 0, s
 
+// the RHS form of the row gather: the material form m, the grip form and the
+// load form by the arguments
+template <class M, class LD>
+static void assemble_rhs_launch(hipStream_t s, int64_t N, const double* xyz, const int32_t* slice_ptr,
+                                const int32_t* row_len, const int32_t* s_col, const int32_t* s_elem,
+                                const uint8_t* active, M m, int64_t G, double* val, double* diag,
+                                const AsmRhs& rhs) {
+  if (rhs.field)
+    hipLaunchKernelGGL((k_assemble<true, M, GripField, LD>), MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, xyz,
+                       slice_ptr, row_len, s_col, s_elem, active, m, G, val, diag, rhs);
+  else if (rhs.vec)
+    hipLaunchKernelGGL((k_assemble<true, M, GripVec, LD>), MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, xyz, slice_ptr,
+                       row_len, s_col, s_elem, active, m, G, val, diag, rhs);
+  else
+    hipLaunchKernelGGL((k_assemble<true, M, GripY, LD>), MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, xyz, slice_ptr,
+                       row_len, s_col, s_elem, active, m, G, val, diag, rhs);
+}
+
 void launch_assemble(hipStream_t s, int64_t N, const double* xyz, const int32_t* slice_ptr,
                      const int32_t* row_len, const int32_t* s_col, const int32_t* s_elem,
                      const uint8_t* active, Material m, int64_t G, double* val, double* diag,
                      const AsmRhs* rhs, const double2* sec) {
   const ElemSection ms{sec};
   if (rhs) {  // (the reduction's blocks publish even when N = 0)
-    if (rhs->field && sec)
-      hipLaunchKernelGGL((k_assemble<true, ElemSection, GripField>), MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, xyz,
-                         slice_ptr, row_len, s_col, s_elem, active, ms, G, val, diag, *rhs);
-    else if (rhs->field)
-      hipLaunchKernelGGL((k_assemble<true, Material, GripField>), MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, xyz,
-                         slice_ptr, row_len, s_col, s_elem, active, m, G, val, diag, *rhs);
-    else if (rhs->vec && sec)
-      hipLaunchKernelGGL((k_assemble<true, ElemSection, GripVec>), MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, xyz,
-                         slice_ptr, row_len, s_col, s_elem, active, ms, G, val, diag, *rhs);
-    else if (rhs->vec)
-      hipLaunchKernelGGL((k_assemble<true, Material, GripVec>), MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, xyz,
-                         slice_ptr, row_len, s_col, s_elem, active, m, G, val, diag, *rhs);
+    if (rhs->load.f && sec)
+      assemble_rhs_launch<ElemSection, NodeLoad>(s, N, xyz, slice_ptr, row_len, s_col, s_elem, active, ms, G, val,
+                                                 diag, *rhs);
+    else if (rhs->load.f)
+      assemble_rhs_launch<Material, NodeLoad>(s, N, xyz, slice_ptr, row_len, s_col, s_elem, active, m, G, val, diag,
+                                              *rhs);
     else if (sec)
-      hipLaunchKernelGGL((k_assemble<true, ElemSection>), MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, xyz, slice_ptr,
-                         row_len, s_col, s_elem, active, ms, G, val, diag, *rhs);
+      assemble_rhs_launch<ElemSection, LoadNone>(s, N, xyz, slice_ptr, row_len, s_col, s_elem, active, ms, G, val,
+                                                 diag, *rhs);
     else
-      hipLaunchKernelGGL((k_assemble<true, Material>), MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, xyz, slice_ptr, row_len,
-                         s_col, s_elem, active, m, G, val, diag, *rhs);
+      assemble_rhs_launch<Material, LoadNone>(s, N, xyz, slice_ptr, row_len, s_col, s_elem, active, m, G, val, diag,
+                                              *rhs);
     return;
   }
   if (N <= 0) return;
@@ -1076,24 +1120,37 @@ void launch_assemble_elems(hipStream_t s, int64_t E, int64_t N, const int32_t* e
   if (N > 0) hipLaunchKernelGGL(k_diag_rows, MFEA_GRID(grid_rows(N)), N, slice_ptr, row_len, G, val, diag);
 }
 
+template <class LD>
+static void rhs_init_launch(hipStream_t s, int64_t N, int64_t nf, const int32_t* slice_ptr, const int32_t* row_len,
+                            const int32_t* s_col, const double* val, const double* diag, int64_t G,
+                            const uint8_t* code, double dy_top, double dy_bot, double reg, int precond, double* x,
+                            double* r, double* p, double* dinv, double* partials, unsigned* ticket, double* red_out,
+                            const GripVec* grip, const double* field, LD ld) {
+  if (field)
+    hipLaunchKernelGGL((k_rhs_init<GripField, LD>), MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, nf, slice_ptr, row_len,
+                       s_col, val, diag, G, code, dy_top, dy_bot, reg, precond, x, r, p, dinv, partials, ticket,
+                       red_out, GripField{field}, ld);
+  else if (grip)
+    hipLaunchKernelGGL((k_rhs_init<GripVec, LD>), MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, nf, slice_ptr, row_len,
+                       s_col, val, diag, G, code, dy_top, dy_bot, reg, precond, x, r, p, dinv, partials, ticket,
+                       red_out, *grip, ld);
+  else
+    hipLaunchKernelGGL((k_rhs_init<GripY, LD>), MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, nf, slice_ptr, row_len,
+                       s_col, val, diag, G, code, dy_top, dy_bot, reg, precond, x, r, p, dinv, partials, ticket,
+                       red_out, GripY{}, ld);
+}
 void launch_rhs_init(hipStream_t s, int64_t N, int64_t nf, const int32_t* slice_ptr,
                      const int32_t* row_len, const int32_t* s_col, const double* val,
                      const double* diag, int64_t G, const uint8_t* code, double dy_top,
                      double dy_bot, double reg, int precond, double* x, double* r, double* p,
                      double* dinv, double* partials, unsigned* ticket, double* red_out, const GripVec* grip,
-                     const double* field) {
-  if (field)
-    hipLaunchKernelGGL(k_rhs_init<GripField>, MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, nf, slice_ptr, row_len, s_col,
-                       val, diag, G, code, dy_top, dy_bot, reg, precond, x, r, p, dinv, partials, ticket, red_out,
-                       GripField{field});
-  else if (grip)
-    hipLaunchKernelGGL(k_rhs_init<GripVec>, MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, nf, slice_ptr, row_len, s_col,
-                       val, diag, G, code, dy_top, dy_bot, reg, precond, x, r, p, dinv, partials, ticket, red_out,
-                       *grip);
+                     const double* field, const NodeLoad* load) {
+  if (load)
+    rhs_init_launch(s, N, nf, slice_ptr, row_len, s_col, val, diag, G, code, dy_top, dy_bot, reg, precond, x, r, p,
+                    dinv, partials, ticket, red_out, grip, field, *load);
   else
-    hipLaunchKernelGGL(k_rhs_init<GripY>, MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, nf, slice_ptr, row_len, s_col,
-                       val, diag, G, code, dy_top, dy_bot, reg, precond, x, r, p, dinv, partials,
-                       ticket, red_out, GripY{});
+    rhs_init_launch(s, N, nf, slice_ptr, row_len, s_col, val, diag, G, code, dy_top, dy_bot, reg, precond, x, r, p,
+                    dinv, partials, ticket, red_out, grip, field, LoadNone{});
 }
 
 void launch_init_finalize(hipStream_t s, const double* red, double rtol, double atol, int norm,
@@ -1161,6 +1218,12 @@ void launch_reaction_field(hipStream_t s, int64_t row0, int64_t nrows, int64_t N
   hipLaunchKernelGGL(k_reaction<GripField>, MFEA_GRID(grid_rows(nrows > 0 ? nrows : 1)), row0, nrows, N, slice_ptr,
                      row_len, s_col, val, diag, G, u, partials, ticket, red_out, GripField{field_rows},
                      (double*)nullptr);
+}
+
+void launch_load_work(hipStream_t s, int64_t nf, const NodeLoad& load, double dy_top, const double* u,
+                      double* partials, unsigned* ticket, double* red_out) {
+  hipLaunchKernelGGL(k_load_work, MFEA_GRID(grid_rows(nf > 0 ? nf : 1)), nf, load, dy_top, u, partials, ticket,
+                     red_out);
 }
 
 void launch_stress(hipStream_t s, int64_t E, const int32_t* e2n, const double* xyz,

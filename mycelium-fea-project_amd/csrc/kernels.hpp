@@ -117,6 +117,25 @@ struct GripField {
   const double* d;
 };
 
+// Nodal loads (mfea_set_node_loads): the load policy beside the grip policy.
+// LoadNone: b = 0 − K_fk x_k, the kernels as they were before loads existed.
+// NodeLoad: a free row r takes b[c] = q[c] − k[c], k the grip term accumulated
+// as without loads and
+//   q[c] = fl(amp · f[3r + c]) + 0,  amp = dy_top (prop) or 1 (a dead load:
+//   the product is the stored value), 0 where fl[r] is set
+// f: 3 doubles per free row in Pattern row order; fl: a byte per free row, 1 on
+// the rows of floating pieces (launch_floating's mask in row order) — their
+// load is dropped, so they stay at exactly zero.  (+ 0: a product −0 counts as
+// 0, as a stored −0 does; with f = 0 the bits are LoadNone's.)  The kernels are
+// templates over the two; a launcher picks NodeLoad when its `load` argument is
+// non-null.
+struct LoadNone {};
+struct NodeLoad {
+  const double* f;
+  const uint8_t* fl;
+  int32_t prop;
+};
+
 // ---- launchers (defined in kernels.hip) -------------------------------------
 // The GAMG solves' RHS formed in the assembly's row pass (k_amg_rhs's work:
 // b = 0 − K_fk x_k of the free rows into r, the prescribed x of the others,
@@ -131,6 +150,8 @@ struct AsmRhs {
   // a grip field (non-null: the GripField kernel, whatever vec says): 3 doubles
   // per known row, at least 3 readable
   const double* field;
+  // nodal loads (load.f non-null: the NodeLoad kernels)
+  NodeLoad load;
   // row classes by position (symbolic.hpp Pattern): top grip rows
   // [nf, top_end), bottom rows [top_end, bot_end), ghost rows after
   int64_t top_end, bot_end;
@@ -165,7 +186,8 @@ void launch_rhs_init(hipStream_t s, int64_t N, int64_t nf, const int32_t* slice_
                      const double* diag, int64_t G, const uint8_t* code, double dy_top,
                      double dy_bot, double reg, int precond, double* x, double* r, double* p,
                      double* dinv, double* partials, unsigned* ticket, double* red_out,
-                     const GripVec* grip = nullptr, const double* field = nullptr);
+                     const GripVec* grip = nullptr, const double* field = nullptr,
+                     const NodeLoad* load = nullptr);
 
 void launch_init_finalize(hipStream_t s, const double* red, double rtol, double atol, int norm,
                           int max_it, double reg, Slot* slots, SolveState* st);
@@ -208,6 +230,14 @@ void launch_reaction_field(hipStream_t s, int64_t row0, int64_t nrows, int64_t N
                            const int32_t* row_len, const int32_t* s_col, const double* val, const double* diag,
                            int64_t G, const double* u, double* partials, unsigned* ticket, double* red_out,
                            const double* field_rows);
+
+// The work of the nodal loads (mfea_get_load_work): red_out[0] = Σ over the
+// free rows r < nf with fl[r] == 0 of
+//   (q[0]·u[0] + q[1]·u[1]) + q[2]·u[2],  q as NodeLoad forms it from dy_top,
+// f64 products and sums in this order, nothing fused; the rows reduced in
+// launch_reaction's fixed order, one launch, launch_reaction's partials.
+void launch_load_work(hipStream_t s, int64_t nf, const NodeLoad& load, double dy_top, const double* u,
+                      double* partials, unsigned* ticket, double* red_out);
 
 // owned (multi-partition): count only elements this partition reports; NULL = all.
 // fail_list / fail_cnt: the (owned) elements that fail in this launch are
@@ -337,7 +367,7 @@ void launch_spmv_csr(hipStream_t s, int j, int64_t n, const int64_t* indptr,
 void launch_cg_rhs(hipStream_t s, const SellOp& op, const uint8_t* code, double dy_top,
                    double dy_bot, double reg, int precond, const CgVecs& v, double* partials,
                    unsigned* ticket, double* red_out, const GripVec* grip = nullptr,
-                   const double* field = nullptr);
+                   const double* field = nullptr, const NodeLoad* load = nullptr);
 // part: 2 parity buffers × [4][kCgMaxPartials] block partials (cg.hip)
 constexpr int kCgMaxPartials = 512;
 // k_cg_first: w₀ = A u₀; block partials (γ₀, δ₀, r·r, u·u) → part parity 0;

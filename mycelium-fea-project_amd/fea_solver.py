@@ -265,7 +265,7 @@ def complete_grip_field(grip_field, n_nodes, top, bot, grip_direction=None):
 def fea_solver(results_dir, tol=GRIP_LENGTH, *, rtol=None, max_it=None, precond=None,
                out_format="python", verbose=True, nparts=1, npy=False, device_run=False,
                events=False, tie_rtol=1e-9, max_events=None, element_props=None, grip_direction=None,
-               energy=False, grip_field=None):
+               energy=False, grip_field=None, node_loads=None, load_mode="dead"):
     """The reference step loop (src/fea_solver.py:186-335) with the hot path on device.
 
     Reads <results_dir>/nodes.csv + elements.csv, runs N_STEPS load steps and
@@ -324,6 +324,16 @@ def fea_solver(results_dir, tol=GRIP_LENGTH, *, rtol=None, max_it=None, precond=
     keeps total_displacement = dy_top − dy_bot; total_force is the generalised
     force of the top band, Σ d_n·(K U)_n over its nodes.
 
+    node_loads (one process, one partition): a CSV file with the columns
+    node_id,fx,fy,fz (mfea.loads.read_csv) or an n_nodes x 3 array — a force on
+    every free node listed (Engine.set_node_loads); grip nodes listed are
+    ignored, and the load on a piece cut off from both grips is dropped.
+    load_mode "dead": the load as given at every step; "proportional": dy_top
+    times it.  Works with the ramp, device_run, element_props, grip_direction,
+    grip_field and energy; with events only in proportional mode (a dead load
+    makes the response affine in the load factor).  The records keep their
+    meaning: total_force is the reaction of the top band.
+
     energy=True (one process, one partition): the strain energy of every record
     row, split into its axial and bending parts (Engine.energy /
     mfea_get_energy), each row on the activity its K was assembled from — the
@@ -345,6 +355,14 @@ def fea_solver(results_dir, tol=GRIP_LENGTH, *, rtol=None, max_it=None, precond=
         grip_direction = parse_grip_direction(grip_direction)
     if grip_field is not None and (world > 1 or nparts > 1):
         raise ValueError("grip_field needs one process and one partition (world == 1, nparts == 1)")
+    if node_loads is not None:
+        if world > 1 or nparts > 1:
+            raise ValueError("node_loads needs one process and one partition (world == 1, nparts == 1)")
+        if load_mode not in ("dead", "proportional"):
+            raise ValueError(f"load_mode must be 'dead' or 'proportional', not {load_mode!r}")
+        if events and load_mode != "proportional":
+            raise ValueError("events with node_loads needs load_mode 'proportional' (a dead load makes the "
+                             "response affine in the load factor)")
     if element_props is not None and (world > 1 or nparts > 1):
         raise ValueError("element_props needs one process and one partition (world == 1, nparts == 1)")
     if events and (world > 1 or nparts > 1):
@@ -382,6 +400,14 @@ def fea_solver(results_dir, tol=GRIP_LENGTH, *, rtol=None, max_it=None, precond=
     eng.set_active(None)
     if grip_field is not None:  # (set_mesh cleared the one the process-wide handle may have held)
         eng.set_grip_field(complete_grip_field(grip_field, n_nodes, top, bot, grip_direction))
+    if node_loads is not None:  # (set_mesh cleared the ones the process-wide handle may have held)
+        from mfea import loads as _loads
+        if isinstance(node_loads, (str, os.PathLike)):
+            node_loads = _loads.read_csv(node_loads, n_nodes)
+        node_loads = np.asarray(node_loads, dtype=np.float64)
+        if node_loads.size != 3 * n_nodes:
+            raise ValueError(f"node_loads must have one row per node ({n_nodes})")
+        eng.set_node_loads(node_loads.reshape(n_nodes, 3), load_mode)
     if element_props is not None:
         props = (element_props if isinstance(element_props, dict)
                  else read_element_props(element_props, n_elems))
@@ -607,6 +633,13 @@ def main(argv=None):
                          "free nodes listed are ignored.  force_displacement.csv keeps total_displacement = "
                          "dy_top - dy_bot, total_force is the generalised force of the top band "
                          "(one process, one partition)")
+    ap.add_argument("--node-loads", metavar="FILE.csv", default=None,
+                    help="a force per free node: CSV with the header node_id,fx,fy,fz; nodes not listed carry "
+                         "none, grip nodes listed are ignored, the load on a piece cut off from both grips is "
+                         "dropped (one process, one partition)")
+    ap.add_argument("--load-mode", choices=["dead", "proportional"], default="dead",
+                    help="--node-loads: dead, the load as given at every step, or proportional, dy_top times "
+                         "it (--events takes proportional loads only)")
     a = ap.parse_args(argv)
     if a.energy and a.parts > 1:
         print("fea_solver: --energy needs one partition (--parts 1)", file=sys.stderr)
@@ -633,6 +666,21 @@ def main(argv=None):
         except (ValueError, OSError) as e:
             print(f"fea_solver: --grip-field: {e}", file=sys.stderr)
             sys.exit(2)
+    node_loads = None
+    if a.node_loads is not None:
+        if a.parts > 1:
+            print("fea_solver: --node-loads needs one partition (--parts 1)", file=sys.stderr)
+            sys.exit(2)
+        if a.events and a.load_mode != "proportional":
+            print("fea_solver: --events with --node-loads needs --load-mode proportional", file=sys.stderr)
+            sys.exit(2)
+        try:
+            from mfea import loads
+            n_nodes = len(pd.read_csv(os.path.join(a.results_dir, "nodes.csv")))
+            node_loads = loads.read_csv(a.node_loads, n_nodes)
+        except (ValueError, OSError) as e:
+            print(f"fea_solver: --node-loads: {e}", file=sys.stderr)
+            sys.exit(2)
     props = None
     if a.element_props is not None:
         try:
@@ -647,7 +695,8 @@ def main(argv=None):
                         "bjacobi": _capi.PC_BLOCK_JACOBI, "sor": _capi.PC_SOR, "icc": _capi.PC_ICC}[a.pc],
                out_format=a.format, nparts=a.parts, npy=a.npy, device_run=a.device_run,
                events=a.events, tie_rtol=a.tie_rtol, max_events=a.max_events, element_props=props,
-               grip_direction=grip, energy=a.energy, grip_field=field)
+               grip_direction=grip, energy=a.energy, grip_field=field, node_loads=node_loads,
+               load_mode=a.load_mode)
 
 
 if __name__ == "__main__":

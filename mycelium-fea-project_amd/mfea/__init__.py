@@ -9,5 +9,7 @@ from ._capi import (Engine, MfeaError, SolverFailure, SolveOpts, Stats, abi_vers
                     GrowParams, grow_params, scaled_grow_params, grow_network,
                     RunRecords, RUN_COMPLETE, RUN_NO_ACTIVE,
                     EventOpts, EventOut, EventRecords, event_opts, event_envelope,
-                    EVENTS_COMPLETE, EVENTS_LAMBDA_MAX, EVENTS_UNLOADED, ElementProps)
+                    EVENTS_COMPLETE, EVENTS_LAMBDA_MAX, EVENTS_UNLOADED, ElementProps,
+                    LOAD_DEAD, LOAD_PROPORTIONAL)
 from . import fields  # noqa: F401
+from . import loads  # noqa: F401

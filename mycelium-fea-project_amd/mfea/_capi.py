@@ -30,6 +30,7 @@ MESH_SKIP_INVALID = 1
 RUN_COMPLETE, RUN_NO_ACTIVE = 0, 1  # mfea_run's stop_reason (or EMAXIT / EBREAKDOWN)
 # mfea_run_events' stop_reason (or EMAXIT / EBREAKDOWN)
 EVENTS_COMPLETE, EVENTS_LAMBDA_MAX, EVENTS_UNLOADED = 0, 1, 2
+LOAD_DEAD, LOAD_PROPORTIONAL = 0, 1  # mfea_set_node_loads's mode
 
 
 class SolveOpts(C.Structure):
@@ -130,6 +131,9 @@ _sig = {
     "mfea_set_grip_field": (C.c_int, [_P, _P]),
     "mfea_get_grip_field": (C.c_int, [_P, _P, C.POINTER(C.c_int32)]),
     "mfea_get_grip_work": (C.c_int, [_P, _P, _P]),
+    "mfea_set_node_loads": (C.c_int, [_P, _P, C.c_int32]),
+    "mfea_get_node_loads": (C.c_int, [_P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mfea_get_load_work": (C.c_int, [_P, _P]),
     "mfea_get_energy": (C.c_int, [_P, _P, _P, _P, C.POINTER(ElementEnergy)]),
     "mfea_set_mesh": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_uint32]),
     "mfea_set_bc": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P]),
@@ -583,6 +587,45 @@ class Engine:
         top, bot = np.empty(1), np.empty(1)
         _check(_lib.mfea_get_grip_work(self._h, _ptr(top), _ptr(bot)))
         return float(top[0]), float(bot[0])
+
+    LOAD_MODES = {"dead": LOAD_DEAD, "proportional": LOAD_PROPORTIONAL}
+
+    def set_node_loads(self, loads=None, mode="dead"):
+        """A force vector per free node (mfea_set_node_loads): loads is
+        n_nodes x 3 in the order of the mesh's nodes, row n the force on node n;
+        rows of grip nodes are ignored.  mode "dead": the load as given, whatever
+        the amplitudes; "proportional": dy_top times the row, the load per unit
+        of the top amplitude.  The load on a piece cut off from both grips is
+        dropped (the piece stays at zero).  None: no loads.  mfea.loads builds
+        the usual ones.  The library copies the array."""
+        if loads is None:
+            _check(_lib.mfea_set_node_loads(self._h, None, LOAD_DEAD))
+            return
+        m = self.LOAD_MODES.get(mode, mode)
+        if isinstance(m, str):
+            raise ValueError(f"mode must be 'dead' or 'proportional', not {mode!r}")
+        a = np.ascontiguousarray(loads, dtype=np.float64)
+        if hasattr(self, "_xyz") and a.size != 3 * self.n_nodes:
+            raise ValueError(f"loads must have three entries per node ({self.n_nodes} nodes)")
+        _check(_lib.mfea_set_node_loads(self._h, _ptr(a), int(m)))
+
+    def node_loads(self):
+        """(loads, mode, is_set): the stored n_nodes x 3 loads (zeros without
+        any), "dead" or "proportional" (mfea_get_node_loads)."""
+        if not hasattr(self, "_xyz"):  # (no mesh yet: the library's MFEA_ESTATE)
+            _check(_lib.mfea_get_node_loads(self._h, None, None, None))
+        out = np.empty((self.n_nodes, 3), dtype=np.float64)
+        mode, is_set = C.c_int32(0), C.c_int32(0)
+        _check(_lib.mfea_get_node_loads(self._h, _ptr(out), C.byref(mode), C.byref(is_set)))
+        return out, ("proportional" if mode.value == LOAD_PROPORTIONAL else "dead"), bool(is_set.value)
+
+    def load_work(self):
+        """The work of the nodal loads on the current U, the sum of q_n . u_n
+        over the free nodes that are not floating, with the amplitudes of the
+        last solve (mfea_get_load_work); 0.0 without loads."""
+        w = np.empty(1)
+        _check(_lib.mfea_get_load_work(self._h, _ptr(w)))
+        return float(w[0])
 
     ENERGY_ROWS = ("w_axial", "w_bending", "g_axial", "g_bending")
 

@@ -61,27 +61,29 @@ def uniform(n_nodes, nodes, vec):
     return out
 
 
-def read_csv(path, n_nodes):
+def read_csv(path, n_nodes, columns=COLUMNS):
     """The field of a CSV file with the columns node_id, dx, dy, dz (a header
     line, one row per listed node, any order).  Returns (field, listed): the
     n_nodes x 3 array and the boolean mask of the nodes the file lists.
     ValueError, naming the file, for a missing column, a duplicate or
-    out-of-range node id, or a value that is not finite."""
+    out-of-range node id, or a value that is not finite.  ``columns``: other
+    names for the four columns (mfea.loads.read_csv: node_id, fx, fy, fz)."""
+    names = ",".join(columns)
     n_nodes = int(n_nodes)
     field = np.zeros((n_nodes, 3), dtype=np.float64)
     listed = np.zeros(n_nodes, dtype=bool)
     with open(path, newline="") as f:
         rd = csv.reader(f)
         header = [h.strip() for h in next(rd, [])]
-        for col in COLUMNS:
+        for col in columns:
             if col not in header:
-                raise ValueError(f"{path}: missing column {col!r} (columns: node_id,dx,dy,dz)")
-        at = [header.index(col) for col in COLUMNS]
+                raise ValueError(f"{path}: missing column {col!r} (columns: {names})")
+        at = [header.index(col) for col in columns]
         for line, row in enumerate(rd, start=2):
             if not row or all(not c.strip() for c in row):
                 continue
             if len(row) <= max(at):
-                raise ValueError(f"{path}:{line}: missing column (a row needs node_id,dx,dy,dz)")
+                raise ValueError(f"{path}:{line}: missing column (a row needs {names})")
             try:
                 nid = float(row[at[0]])
                 d = [float(row[k]) for k in at[1:]]
