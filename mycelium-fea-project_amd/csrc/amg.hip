@@ -1406,7 +1406,7 @@ __global__ __launch_bounds__(kBlock) void k_amg_row0_inverse(AmgCg cg, int32_t* 
 // vcycle_entry: level 0's D⁻¹ and ω must be current, i.e. the setup kept),
 // and the reduction's last block k_cg_init_finalize's: the state, and the
 // zeroing of the partial buffers.
-// GM: GripY, or GripVec / GripField — k_amg_rhs<GM>'s row body (kernels.hpp).
+// GM: GripY, or GripVec / GripField — k_amg_rhs<GM>'s row body (bc_form.hpp).
 // LD: LoadNone, or NodeLoad — k_amg_rhs<GM, LD>'s.
 template <int ND, class GM, class LD = LoadNone>
 __global__ __launch_bounds__(kBlock) void k_amg_start(SellOp op, const uint8_t* __restrict__ code, double dy_top,
@@ -2329,48 +2329,22 @@ void launch_amg_row0_inverse(hipStream_t s, const AmgCg& cg, int32_t* inv, int64
   hipLaunchKernelGGL(k_amg_row0_inverse, rows_grid(cg.hi - cg.lo), dim3(kBlock), 0, s, cg, inv);
 }
 
-// the grip form g and the load form ld chosen: the kernel by the lanes' DOFs
-template <class GM, class LD>
-static void amg_start_launch(hipStream_t s, int nd, const SellOp& op, const uint8_t* code, double dy_top,
-                             double dy_bot, const CgVecs& v, double* partials, unsigned* ticket, double* red_out,
-                             const AmgLevD& L0, const AmgCg& cg, const int32_t* inv, double rtol, double atol,
-                             int norm, int max_it, double reg, SolveState* st, double* zero, int64_t nzero, GM g,
-                             LD ld) {
-  const dim3 grid((unsigned)grid_rows(op.N > 0 ? op.N : 1));  // k_amg_rhs's (launch_cg_rhs)
-  if (nd == 2)
-    hipLaunchKernelGGL((k_amg_start<2, GM, LD>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials,
-                       ticket, red_out, L0, cg, inv, rtol, atol, norm, max_it, reg, st, zero, nzero, g, ld);
-  else
-    hipLaunchKernelGGL((k_amg_start<3, GM, LD>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials,
-                       ticket, red_out, L0, cg, inv, rtol, atol, norm, max_it, reg, st, zero, nzero, g, ld);
-}
-template <class LD>
-static void amg_start_grip(hipStream_t s, int nd, const SellOp& op, const uint8_t* code, double dy_top,
-                           double dy_bot, const CgVecs& v, double* partials, unsigned* ticket, double* red_out,
-                           const AmgLevD& L0, const AmgCg& cg, const int32_t* inv, double rtol, double atol,
-                           int norm, int max_it, double reg, SolveState* st, double* zero, int64_t nzero,
-                           const GripVec* grip, const double* field, LD ld) {
-  if (field)
-    amg_start_launch(s, nd, op, code, dy_top, dy_bot, v, partials, ticket, red_out, L0, cg, inv, rtol, atol, norm,
-                     max_it, reg, st, zero, nzero, GripField{field}, ld);
-  else if (grip)
-    amg_start_launch(s, nd, op, code, dy_top, dy_bot, v, partials, ticket, red_out, L0, cg, inv, rtol, atol, norm,
-                     max_it, reg, st, zero, nzero, *grip, ld);
-  else
-    amg_start_launch(s, nd, op, code, dy_top, dy_bot, v, partials, ticket, red_out, L0, cg, inv, rtol, atol, norm,
-                     max_it, reg, st, zero, nzero, GripY{}, ld);
-}
+// the grip and load forms by bc (bc_form.hpp), the kernel by the lanes' DOFs
 void launch_amg_start(hipStream_t s, int nd, const SellOp& op, const uint8_t* code, double dy_top, double dy_bot,
                       const CgVecs& v, double* partials, unsigned* ticket, double* red_out, const AmgLevD& L0,
                       const AmgCg& cg, const int32_t* inv, double rtol, double atol, int norm, int max_it,
-                      double reg, SolveState* st, double* zero, int64_t nzero, const GripVec* grip,
-                      const double* field, const NodeLoad* load) {
-  if (load)
-    amg_start_grip(s, nd, op, code, dy_top, dy_bot, v, partials, ticket, red_out, L0, cg, inv, rtol, atol, norm,
-                   max_it, reg, st, zero, nzero, grip, field, *load);
-  else
-    amg_start_grip(s, nd, op, code, dy_top, dy_bot, v, partials, ticket, red_out, L0, cg, inv, rtol, atol, norm,
-                   max_it, reg, st, zero, nzero, grip, field, LoadNone{});
+                      double reg, SolveState* st, double* zero, int64_t nzero, const BcForm& bc) {
+  const dim3 grid((unsigned)grid_rows(op.N > 0 ? op.N : 1));  // k_amg_rhs's (launch_cg_rhs)
+  with_bc(bc, [&](auto g, auto ld) {
+    using GM = decltype(g);
+    using LD = decltype(ld);
+    if (nd == 2)
+      hipLaunchKernelGGL((k_amg_start<2, GM, LD>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials,
+                         ticket, red_out, L0, cg, inv, rtol, atol, norm, max_it, reg, st, zero, nzero, g, ld);
+    else
+      hipLaunchKernelGGL((k_amg_start<3, GM, LD>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials,
+                         ticket, red_out, L0, cg, inv, rtol, atol, norm, max_it, reg, st, zero, nzero, g, ld);
+  });
 }
 
 template <int ND, int BS>

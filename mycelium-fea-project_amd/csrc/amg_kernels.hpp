@@ -337,12 +337,12 @@ void launch_amg_up_w(hipStream_t s, int nd, int j, bool first, const AmgLevD& L0
 // inv[n_rows]: Pattern row → level-0 row of cg.row0, −1 elsewhere
 void launch_amg_row0_inverse(hipStream_t s, const AmgCg& cg, int32_t* inv, int64_t n_rows);
 // launch_cg_rhs (precond 2) + launch_cg_init_finalize + launch_amg_cg_init as
-// one launch, the same bits; only on hierarchy values that are current
+// one launch, the same bits; only on hierarchy values that are current.  bc:
+// the grip and load forms (bc_form.hpp with_bc picks the instantiation)
 void launch_amg_start(hipStream_t s, int nd, const SellOp& op, const uint8_t* code, double dy_top, double dy_bot,
                       const CgVecs& v, double* partials, unsigned* ticket, double* red_out, const AmgLevD& L0,
                       const AmgCg& cg, const int32_t* inv, double rtol, double atol, int norm, int max_it,
-                      double reg, SolveState* st, double* zero, int64_t nzero, const GripVec* grip = nullptr,
-                      const double* field = nullptr, const NodeLoad* load = nullptr);
+                      double reg, SolveState* st, double* zero, int64_t nzero, const BcForm& bc);
 // block partials of ‖r‖² alone, bitwise the next w launch's (component 2 of
 // cpart = [4][kCgMaxPartials]): the closing check of a chunk, launch_cg_advance
 void launch_amg_rnorm(hipStream_t s, int nd, const AmgCg& cg, double* cpart);

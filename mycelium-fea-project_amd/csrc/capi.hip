@@ -128,10 +128,10 @@ struct Part {
   DevBuf<uint8_t> en_act;
   DevBuf<unsigned> en_tix;
   // mfea_set_grip_field: the field's vectors of the known rows in row order
-  // (kernels.hpp GripField; at least 3 doubles), uploaded by the setter and at
+  // (bc_form.hpp GripField; at least 3 doubles), uploaded by the setter and at
   // each build; mfea_get_grip_work's outputs (sums[0..2] of a band, the value)
   DevBuf<double> grip_d, gw_red;
-  // mfea_set_node_loads: the loads of the free rows in row order (kernels.hpp
+  // mfea_set_node_loads: the loads of the free rows in row order (bc_form.hpp
   // NodeLoad; at least 3 doubles), uploaded by the setter and at each build;
   // the floating mask of the free rows in row order (launch_floating, label
   // NULL) with the act_gen it reflects (−1: none yet) — recomputed only while
@@ -298,38 +298,35 @@ struct mfea_handle : Options {
   const double2* sec_d() const { return pe_sec.empty() ? nullptr : reinterpret_cast<const double2*>(pe_sec_d.ptr); }
   const double* Ee_d() const { return pe_E.empty() ? nullptr : pe_E_d.ptr; }
   const double* strength_d() const { return pe_S.empty() ? nullptr : pe_S_d.ptr; }
-  // mfea_set_grip_motion (one partition): the directions of the grip motion,
-  // handle state as the material is.  The tensile test's pair takes the
-  // kernels as they were (grip_arg NULL: the GripY instantiations); any other
-  // the GripVec ones.  Nothing of K or the hierarchies depends on them.
-  GripVec grip{{0.0, 1.0, 0.0}, {0.0, 1.0, 0.0}};
-  bool grip_default() const {
-    return grip.top[0] == 0.0 && grip.top[1] == 1.0 && grip.top[2] == 0.0 && grip.bot[0] == 0.0 &&
-           grip.bot[1] == 1.0 && grip.bot[2] == 0.0;
-  }
-  const GripVec* grip_arg() const { return grip_default() ? nullptr : &grip; }
-  // mfea_set_grip_field (one partition): a vector per node, original node
-  // order, host copy.  While set it takes the place of the two directions
-  // everywhere (they are kept, and read nowhere): the GripField kernels.
-  std::vector<double> field;
-  bool has_field = false;
-  bool grip_z() const {
-    if (!has_field) return grip.top[2] != 0.0 || grip.bot[2] != 0.0;
-    for (size_t n = 2; n < field.size(); n += 3)
-      if (field[n] != 0.0) return true;
-    return false;
-  }
-  // mfea_set_node_loads (one partition): a force vector per node, original
-  // node order, host copy; the mode; dy_top of the last solve (mfea_get_load_work)
-  std::vector<double> loads;
-  bool has_loads = false;
-  int32_t load_mode = MFEA_LOAD_DEAD;
-  double load_dy_top = 0.0;
-  bool load_z() const {
-    for (size_t n = 2; n < loads.size(); n += 3)
-      if (loads[n] != 0.0) return true;
-    return false;
-  }
+  // What is prescribed on the boundary and the free nodes (one partition),
+  // handle state as the material is; nothing of K or the hierarchies depends
+  // on it.  form() is what every launcher is told (bc_form.hpp BcForm).
+  struct Loading {
+    // mfea_set_grip_motion: the directions of the grip motion.  The tensile
+    // test's pair takes the kernels as they were (the GripY instantiations);
+    // any other the GripVec ones.
+    GripVec grip{{0.0, 1.0, 0.0}, {0.0, 1.0, 0.0}};
+    // mfea_set_grip_field: a vector per node, original node order, host copy.
+    // While set it takes the place of the two directions everywhere (they are
+    // kept, and read nowhere): the GripField kernels.
+    NodeVectors field;
+    // mfea_set_node_loads: a force vector per node, original node order, host
+    // copy; the mode; dy_top of the last solve (mfea_get_load_work)
+    NodeVectors loads;
+    int32_t load_mode = MFEA_LOAD_DEAD;
+    double load_dy_top = 0.0;
+    bool grip_default() const {
+      return grip.top[0] == 0.0 && grip.top[1] == 1.0 && grip.top[2] == 0.0 && grip.bot[0] == 0.0 &&
+             grip.bot[1] == 1.0 && grip.bot[2] == 0.0;
+    }
+    bool grip_z() const { return field.set ? field.z() : grip.top[2] != 0.0 || grip.bot[2] != 0.0; }
+    bool load_z() const { return loads.z(); }
+    // (the field's and the loads' rows of pt: upload_rows, at the setters and at each build)
+    BcForm form(const Part& pt) const {
+      return BcForm{grip_default() ? nullptr : &grip, field.set ? pt.grip_d.ptr : nullptr,
+                    loads.set ? &pt.ld : nullptr};
+    }
+  } bc;
   // host-side mesh/BC (original order)
   int64_t N = 0, Ecount = 0;
   std::vector<double> xyz;
@@ -620,44 +617,37 @@ int upload_props(mfea_handle* h) {
   return 0;
 }
 
-// The grip field's vectors of the known rows, gathered into Pattern row order
-// (row j at 3·(j − n_free)) and uploaded; waited for, before and after.
-int upload_field(mfea_handle* h, Part& pt) {
-  const Pattern& P = pt.P;
-  const int64_t nk = P.n_nodes - P.n_free;
-  std::vector<double> rows((size_t)3 * std::max<int64_t>(nk, 1), 0.0);
-  for (int64_t r = 0; r < nk; ++r)
-    for (int c = 0; c < 3; ++c) rows[3 * r + c] = h->field[3 * (size_t)P.perm[P.n_free + r] + c];
+// Rows [row0, row0 + n) of a per-node array gathered into Pattern row order
+// (row row0 + r at 3r; at least 3 doubles) and uploaded into dst; waited for,
+// before and after.
+static int upload_rows(mfea_handle* h, const Pattern& P, const std::vector<double>& nodes, int64_t row0, int64_t n,
+                       DevBuf<double>& dst) {
+  std::vector<double> rows((size_t)3 * std::max<int64_t>(n, 1), 0.0);
+  for (int64_t r = 0; r < n; ++r)
+    for (int c = 0; c < 3; ++c) rows[3 * r + c] = nodes[3 * (size_t)P.perm[row0 + r] + c];
   HIPC(hipStreamSynchronize(h->stream));
-  HIPC(pt.grip_d.alloc(rows.size()));
-  HIPC(hmemcpy(h, pt.grip_d.ptr, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIPC(dst.alloc(rows.size()));
+  HIPC(hmemcpy(h, dst.ptr, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice));
   return 0;
 }
-// the kernels' `field` argument: null without a grip field
-const double* field_arg(const mfea_handle* h, const Part& pt) { return h->has_field ? pt.grip_d.ptr : nullptr; }
-
-// The nodal loads of the free rows, gathered into Pattern row order and
-// uploaded; waited for, before and after.  The floating mask of this build
-// starts as zeros and counts as not computed (ensure_load_mask); it depends on
-// the activity alone, so other loads on the same build keep it.
+// The grip field's vectors of the known rows (row j at 3·(j − n_free)).
+int upload_field(mfea_handle* h, Part& pt) {
+  return upload_rows(h, pt.P, h->bc.field.v, pt.P.n_free, pt.P.n_nodes - pt.P.n_free, pt.grip_d);
+}
+// The nodal loads of the free rows.  The floating mask of this build starts as
+// zeros and counts as not computed (ensure_load_mask); it depends on the
+// activity alone, so other loads on the same build keep it.
 int upload_loads(mfea_handle* h, Part& pt) {
   const Pattern& P = pt.P;
-  std::vector<double> rows((size_t)3 * std::max<int64_t>(P.n_free, 1), 0.0);
-  for (int64_t r = 0; r < P.n_free; ++r)
-    for (int c = 0; c < 3; ++c) rows[3 * r + c] = h->loads[3 * (size_t)P.perm[r] + c];
-  HIPC(hipStreamSynchronize(h->stream));
-  HIPC(pt.ld_f.alloc(rows.size()));
-  HIPC(hmemcpy(h, pt.ld_f.ptr, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice));
+  RC(upload_rows(h, P, h->bc.loads.v, 0, P.n_free, pt.ld_f));
   if (!pt.ld_mask.ptr) {
     HIPC(pt.ld_mask.alloc(std::max<int64_t>(P.n_free, 1)));
     HIPC(hmemset(h, pt.ld_mask.ptr, 0, std::max<int64_t>(P.n_free, 1)));
     pt.ld_mask_gen = -1;
   }
-  pt.ld = NodeLoad{pt.ld_f.ptr, pt.ld_mask.ptr, h->load_mode == MFEA_LOAD_PROPORTIONAL ? 1 : 0};
+  pt.ld = NodeLoad{pt.ld_f.ptr, pt.ld_mask.ptr, h->bc.load_mode == MFEA_LOAD_PROPORTIONAL ? 1 : 0};
   return 0;
 }
-// the kernels' `load` argument: null without loads
-const NodeLoad* load_arg(const mfea_handle* h, const Part& pt) { return h->has_loads ? &pt.ld : nullptr; }
 
 // The floating mask the load kernels read, of the device's current activity:
 // recomputed (launch_floating in row order, four launches on the stream, no
@@ -665,7 +655,7 @@ const NodeLoad* load_arg(const mfea_handle* h, const Part& pt) { return h->has_l
 // are set.  Called in front of every assembly and step, outside any capture,
 // so the mask is that of the activity the step's K is assembled from.
 int ensure_load_mask(mfea_handle* h) {
-  if (!h->has_loads || h->parts.size() != 1) return 0;
+  if (!h->bc.loads.set || h->parts.size() != 1) return 0;
   Part& pt = *h->parts[0];
   const Pattern& P = pt.P;
   if (pt.ld_mask_gen == h->act_gen || P.n_free == 0) return 0;
@@ -720,7 +710,7 @@ int order_mode(const mfea_handle* h) { return h->opt_order; }
 // (grip_z: of the field's rows while a grip field is set; load_z: a nodal load
 // with a z entry takes the solution out of the plane as well)
 int lane_dofs(const mfea_handle* h) {
-  return (h->planar && h->opt_lane_dof != 3 && !h->grip_z() && !h->load_z()) ? 2 : 3;
+  return (h->planar && h->opt_lane_dof != 3 && !h->bc.grip_z() && !h->bc.load_z()) ? 2 : 3;
 }
 
 // Waits for an event.  Partitioned over RCCL: polls with a deadline and the
@@ -920,11 +910,11 @@ int ensure_built(mfea_handle* h) {
   const bool dm = h->world > 1 || h->nparts > 1;
   if (dm && h->has_props())
     return fail(MFEA_ESTATE, "per-element properties: one partition per handle (mfea_set_element_props(h, NULL) first)");
-  if (dm && h->has_field)
+  if (dm && h->bc.field.set)
     return fail(MFEA_ESTATE, "grip field: one partition per handle (mfea_set_grip_field(h, NULL) first)");
-  if (dm && h->has_loads)
+  if (dm && h->bc.loads.set)
     return fail(MFEA_ESTATE, "nodal loads: one partition per handle (mfea_set_node_loads(h, NULL, 0) first)");
-  if (dm && !h->grip_default())
+  if (dm && !h->bc.grip_default())
     return fail(MFEA_ESTATE, "grip motion: one partition per handle (set the directions (0,1,0), (0,1,0) first)");
   const int np = h->world > 1 ? 1 : h->nparts;
   const bool skip = (h->mesh_flags & MFEA_MESH_SKIP_INVALID) != 0;
@@ -956,8 +946,8 @@ int ensure_built(mfea_handle* h) {
       pt.mirror = pt.state_mirror.ptr;
     }
     RC(upload_part(h, pt, dm));
-    if (h->has_field) RC(upload_field(h, pt));
-    if (h->has_loads) RC(upload_loads(h, pt));
+    if (h->bc.field.set) RC(upload_field(h, pt));
+    if (h->bc.loads.set) RC(upload_loads(h, pt));
   }
   if (dm) {  // distributed GAMG: the whole mesh's pattern and the node owners
     h->gamg_ok = false;
@@ -1460,7 +1450,7 @@ int solve_impl(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_op
   const CgVecs v = cg_vecs(pt);
   RC(phase_event(h, h->ev[1], s));
   launch_cg_rhs(s, op, pt.code.ptr, dy_top, dy_bot, o->reg, precond, v, pt.partials.ptr, tix(pt, 0),
-                pt.red.ptr, h->grip_arg(), field_arg(h, pt), load_arg(h, pt));
+                pt.red.ptr, h->bc.form(pt));
   launch_cg_init_finalize(s, pt.red.ptr, o->rtol, o->atol, o->norm, o->max_it, o->reg,
                           pt.state.ptr,
                           pt.cg_part.ptr, 2 * 4 * kCgMaxPartials);
@@ -2451,6 +2441,33 @@ void enqueue_amg_entry(mfea_handle* h, Part& pt, bool skip_init = false) {
   launch_amg_cg_update(s, nd, 0, L0, cg, pt.slots.ptr, pt.state.ptr, pt.cg_part.ptr, nullptr, lazy);  // update 0
 }
 
+// The fused RHS of the row gather (kernels.hpp AsmRhs) on pt's vectors: the
+// amplitudes dy[0..1] by value, or (dy NULL) read from the device pair dyp
+static AsmRhs asm_rhs(const mfea_handle* h, Part& pt, const double* dy, const double* dyp) {
+  const Pattern& P = pt.P;
+  const BcForm bc = h->bc.form(pt);
+  AsmRhs q{};
+  q.code = pt.code.ptr;
+  q.top_end = P.n_free + P.n_top;
+  q.bot_end = P.n_nodes - P.n_ghost;
+  if (dy) {
+    q.dy_top = dy[0];
+    q.dy_bot = dy[1];
+  }
+  q.dyp = dyp;
+  q.grip = h->bc.grip;
+  q.vec = bc.grip != nullptr;
+  q.field = bc.field;
+  if (bc.load) q.load = *bc.load;
+  q.nf = P.n_free;
+  q.r = pt.r.ptr;
+  q.x = pt.x.ptr;
+  q.partials = pt.partials.ptr;
+  q.ticket = tix(pt, 0);
+  q.red_out = pt.red.ptr;
+  return q;
+}
+
 // mfea_step's deferred assembly (option step_graph) at the head of the setup
 // graph: the grip displacements from pinned h_red[14..15] (a copy node, read
 // at replay), the row gather with the fused RHS reading them from d_dy, the
@@ -2459,21 +2476,7 @@ void enqueue_step_head(mfea_handle* h, Part& pt, const mfea_solve_opts* o) {
   hipStream_t s = h->stream;
   const Pattern& P = pt.P;
   (void)hipMemcpyAsync(h->d_dy.ptr, h->h_red + 14, 2 * sizeof(double), hipMemcpyHostToDevice, s);
-  AsmRhs q{};
-  q.code = pt.code.ptr;
-  q.top_end = P.n_free + P.n_top;
-  q.bot_end = P.n_nodes - P.n_ghost;
-  q.dyp = h->d_dy.ptr;
-  q.grip = h->grip;
-  q.vec = !h->grip_default();
-  q.field = field_arg(h, pt);
-  if (h->has_loads) q.load = pt.ld;
-  q.nf = P.n_free;
-  q.r = pt.r.ptr;
-  q.x = pt.x.ptr;
-  q.partials = pt.partials.ptr;
-  q.ticket = tix(pt, 0);
-  q.red_out = pt.red.ptr;
+  const AsmRhs q = asm_rhs(h, pt, nullptr, h->d_dy.ptr);
   launch_assemble(s, P.n_nodes, pt.xyz_d.ptr, pt.slice_ptr.ptr, pt.row_len.ptr, pt.s_col.ptr, pt.s_elem.ptr,
                   pt.active.ptr, h->mat, pt.G, pt.val.ptr, pt.diag.ptr, &q, h->sec_d());
   launch_cg_init_finalize(s, pt.red.ptr, o->rtol, o->atol, o->norm, o->max_it, o->reg, pt.state.ptr,
@@ -2675,13 +2678,12 @@ int solve_amg(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opt
       }
       launch_amg_start(s, nd, op, pt.code.ptr, dy_top, dy_bot, v, pt.partials.ptr, tix(pt, 0), pt.red.ptr,
                        pt.amg_lev[0], pt.amg_cg, pt.amg_inv.ptr, o->rtol, o->atol, o->norm, o->max_it, o->reg,
-                       pt.state.ptr, pt.cg_part.ptr, 2 * 4 * kCgMaxPartials, h->grip_arg(),
-                       field_arg(h, pt), load_arg(h, pt));
+                       pt.state.ptr, pt.cg_part.ptr, 2 * 4 * kCgMaxPartials, h->bc.form(pt));
       ++h->amg_start_fused;
     } else {
       if (!rhs_done)
         launch_cg_rhs(s, op, pt.code.ptr, dy_top, dy_bot, o->reg, 2, v, pt.partials.ptr, tix(pt, 0), pt.red.ptr,
-                      h->grip_arg(), field_arg(h, pt), load_arg(h, pt));
+                      h->bc.form(pt));
       if (!start_in_graph)
         launch_cg_init_finalize(s, pt.red.ptr, o->rtol, o->atol, o->norm, o->max_it, o->reg, pt.state.ptr,
                                 pt.cg_part.ptr, 2 * 4 * kCgMaxPartials);
@@ -3632,21 +3634,7 @@ int assemble_impl(mfea_handle* h, mfea_stats* st, const double* rhs_dy = nullptr
     AsmRhs q{};
     const bool rhs = rhs_dy && h->parts.size() == 1;  // (rhs_dy: a one-partition GAMG / SOR / ICC step)
     if (rhs) {
-      q.code = pt.code.ptr;
-      q.top_end = P.n_free + P.n_top;
-      q.bot_end = P.n_nodes - P.n_ghost;
-      q.dy_top = rhs_dy[0];
-      q.dy_bot = rhs_dy[1];
-      q.grip = h->grip;
-      q.vec = !h->grip_default();
-      q.field = field_arg(h, pt);
-      if (h->has_loads) q.load = pt.ld;
-      q.nf = P.n_free;
-      q.r = pt.r.ptr;
-      q.x = pt.x.ptr;
-      q.partials = pt.partials.ptr;
-      q.ticket = tix(pt, 0);
-      q.red_out = pt.red.ptr;
+      q = asm_rhs(h, pt, rhs_dy, nullptr);
       h->rhs_fused = true;
       h->rhs_dy[0] = rhs_dy[0];
       h->rhs_dy[1] = rhs_dy[1];
@@ -3742,6 +3730,28 @@ int local_failures(mfea_handle* h, Part& pt, unsigned c) {
 // the post kernels (reaction, stress / failures) and the read-back of their
 // sums into h_red, ev[5] behind them
 int enqueue_post_work(mfea_handle* h, double max_strain);
+// The generalised force of the band of known rows [row0, row0 + nrows) into
+// *out by the grip form, one launch on the post's partials and ticket set: a
+// grip field Σ d·f of the band's rows; directions the band's reaction vector
+// into sums[0..2] and its product with dir; the tensile test the y sum.
+static void launch_band_force(hipStream_t s, Part& pt, const BcForm& bc, int64_t row0, int64_t nrows,
+                              const double* dir, double* sums, double* out) {
+  const Pattern& P = pt.P;
+  with_grip(bc, [&](auto g) {
+    using GM = decltype(g);
+    if constexpr (std::is_same<GM, GripField>::value)
+      launch_reaction_field(s, row0, nrows, P.n_nodes, pt.slice_ptr.ptr, pt.row_len.ptr, pt.s_col.ptr, pt.val.ptr,
+                            pt.diag.ptr, pt.G, pt.x.ptr, pt.partials.ptr, tix(pt, 3), out,
+                            g.d + 3 * (row0 - P.n_free));
+    else if constexpr (std::is_same<GM, GripVec>::value)
+      launch_reaction3(s, row0, nrows, P.n_nodes, pt.slice_ptr.ptr, pt.row_len.ptr, pt.s_col.ptr, pt.val.ptr,
+                       pt.diag.ptr, pt.G, pt.x.ptr, pt.partials.ptr, tix(pt, 3), sums, dir, out);
+    else
+      launch_reaction(s, row0, nrows, P.n_nodes, pt.slice_ptr.ptr, pt.row_len.ptr, pt.s_col.ptr, pt.val.ptr,
+                      pt.diag.ptr, pt.G, pt.x.ptr, pt.partials.ptr, tix(pt, 3), out);
+  });
+}
+
 int enqueue_post(mfea_handle* h, double max_strain) {
   RC(phase_event(h, h->ev[4], h->stream));
   RC(enqueue_post_work(h, max_strain));
@@ -3761,18 +3771,7 @@ int enqueue_post_work(mfea_handle* h, double max_strain) {
     // (other directions than the tensile test's: the reaction vector of the
     // top rows into red[9..11] and the work-conjugate force into red[4], one launch)
     // (a grip field: the generalised force Σ d·f of the top rows into red[4])
-    if (h->has_field)
-      launch_reaction_field(s, P.n_free, P.n_top, P.n_nodes, pt.slice_ptr.ptr, pt.row_len.ptr, pt.s_col.ptr,
-                            pt.val.ptr, pt.diag.ptr, pt.G, pt.x.ptr, pt.partials.ptr, tix(pt, 3), pt.red.ptr + 4,
-                            pt.grip_d.ptr);
-    else if (h->grip_arg())
-      launch_reaction3(s, P.n_free, P.n_top, P.n_nodes, pt.slice_ptr.ptr, pt.row_len.ptr, pt.s_col.ptr, pt.val.ptr,
-                       pt.diag.ptr, pt.G, pt.x.ptr, pt.partials.ptr, tix(pt, 3), pt.red.ptr + 9, h->grip.top,
-                       pt.red.ptr + 4);
-    else
-      launch_reaction(s, P.n_free, P.n_top, P.n_nodes, pt.slice_ptr.ptr, pt.row_len.ptr, pt.s_col.ptr,
-                      pt.val.ptr, pt.diag.ptr, pt.G, pt.x.ptr, pt.partials.ptr, tix(pt, 3),
-                      pt.red.ptr + 4);
+    launch_band_force(s, pt, h->bc.form(pt), P.n_free, P.n_top, h->bc.grip.top, pt.red.ptr + 9, pt.red.ptr + 4);
     if (dm) HIPC(hipMemsetAsync(pt.fail_cnt.ptr, 0, sizeof(unsigned), s));
     // one partition: the counter is red[6] (read back with the force and the
     // count, no copy of its own), zero here — cleared by the host after the
@@ -3803,7 +3802,7 @@ int enqueue_event_work(mfea_handle* h) {
   hipStream_t s = h->stream;
   Part& pt = part0(h);
   const Pattern& P = pt.P;
-  const bool vec = !h->grip_default() && !h->has_field;
+  const bool vec = !h->bc.grip_default() && !h->bc.field.set;
   if ((int64_t)pt.partials.n < event_scan_partials(P.n_top, P.n_elems, vec))
     return fail(MFEA_EINVAL, "internal: partials too small for the event scan");
   double* eps = h->opt_event_scratch ? pt.eps.ptr : nullptr;
@@ -3831,9 +3830,9 @@ int enqueue_event_work(mfea_handle* h) {
   q.smax_out = pt.red.ptr + 7;
   q.strength = h->strength_d();
   q.vec = vec;
-  for (int c = 0; c < 3; ++c) q.w[c] = h->grip.top[c];
+  for (int c = 0; c < 3; ++c) q.w[c] = h->bc.grip.top[c];
   q.sums = pt.red.ptr + 9;
-  q.field = field_arg(h, pt);  // (the top rows are the first known rows)
+  q.field = h->bc.form(pt).field;  // (the top rows are the first known rows)
   launch_event_scan(s, q);
   EventApply a{};
   a.E = P.n_elems;
@@ -3988,7 +3987,7 @@ int solve_any(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_opt
               mfea_stats* st) {
   h->ev_setup_used = false;
   h->setup_skipped = false;
-  h->load_dy_top = dy_top;  // (mfea_get_load_work: the amplitude of the last solve)
+  h->bc.load_dy_top = dy_top;  // (mfea_get_load_work: the amplitude of the last solve)
   // another preconditioner kind than the last solve's: its setup runs
   if (o->precond != h->last_precond) drop_kept_setup(h);
   h->last_precond = o->precond;
@@ -4144,6 +4143,18 @@ static int grip_changed(mfea_handle* h, int nd0) {
   return 0;
 }
 
+// The shared middle of mfea_set_grip_field and mfea_set_node_loads, behind
+// their checks: the stream drained, then staged (stage_node_vectors) made the
+// state of nv.  *nd0: lane_dofs before the change, for grip_changed.
+static int swap_node_vectors(mfea_handle* h, NodeVectors& nv, std::vector<double>& staged, bool set, int* nd0) {
+  RC(set_device(h));
+  *nd0 = lane_dofs(h);
+  if (h->stream) HIPC(hipStreamSynchronize(h->stream));
+  nv.v.swap(staged);
+  nv.set = set;
+  return 0;
+}
+
 int mfea_set_grip_motion(mfea_handle* h, const double top[3], const double bot[3]) {
   if (!h) return fail(MFEA_EINVAL, "NULL handle");
   // (what the next build will be decides, not the partitions a handle still
@@ -4156,17 +4167,17 @@ int mfea_set_grip_motion(mfea_handle* h, const double top[3], const double bot[3
     if (v[0] == 0.0 && v[1] == 0.0 && v[2] == 0.0)
       return fail(MFEA_EINVAL, "mfea_set_grip_motion: a direction must not be all zero");
   }
-  GripVec g = h->grip;
+  GripVec g = h->bc.grip;
   for (int c = 0; c < 3; ++c) {
     // (+ 0.0: a −0 component is stored as 0 — dy · 0 has the sign of dy either way)
     if (top) g.top[c] = top[c] + 0.0;
     if (bot) g.bot[c] = bot[c] + 0.0;
   }
-  if (std::memcmp(&g, &h->grip, sizeof g) == 0) return 0;
+  if (std::memcmp(&g, &h->bc.grip, sizeof g) == 0) return 0;
   RC(set_device(h));
   const int nd0 = lane_dofs(h);
   if (h->stream) HIPC(hipStreamSynchronize(h->stream));
-  h->grip = g;
+  h->bc.grip = g;
   return grip_changed(h, nd0);
 }
 
@@ -4178,50 +4189,39 @@ int mfea_set_grip_field(mfea_handle* h, const double* field) {
   if (!h) return fail(MFEA_EINVAL, "NULL handle");
   if (!h->has_mesh) return fail(MFEA_ESTATE, "set the mesh before the grip field");
   if (h->world > 1 || h->nparts > 1) return fail(MFEA_ESTATE, "mfea_set_grip_field: one partition per handle");
-  const size_t n = (size_t)3 * h->N;
   std::vector<double> f;
-  if (field) {
-    f.resize(n);
-    for (size_t k = 0; k < n; ++k) {
-      if (!std::isfinite(field[k])) return fail(MFEA_EINVAL, "mfea_set_grip_field: every entry must be finite");
-      f[k] = field[k] + 0.0;  // (a −0 entry is stored as 0, as the directions are)
-    }
-  }
-  if (h->has_field == (field != nullptr) &&
-      (!field || n == 0 || std::memcmp(f.data(), h->field.data(), n * sizeof(double)) == 0))
-    return 0;
-  RC(set_device(h));
-  const int nd0 = lane_dofs(h);
-  if (h->stream) HIPC(hipStreamSynchronize(h->stream));
-  h->field.swap(f);
-  h->has_field = field != nullptr;
+  const VecStage st = stage_node_vectors(h->bc.field, field, (size_t)3 * h->N, f);
+  if (st == VecStage::kNotFinite) return fail(MFEA_EINVAL, "mfea_set_grip_field: every entry must be finite");
+  if (st == VecStage::kSame) return 0;
+  int nd0 = 0;
+  RC(swap_node_vectors(h, h->bc.field, f, field != nullptr, &nd0));
   RC(grip_changed(h, nd0));
-  if (h->has_field && !h->dirty && h->parts.size() == 1) RC(upload_field(h, part0(h)));
+  if (h->bc.field.set && !h->dirty && h->parts.size() == 1) RC(upload_field(h, part0(h)));
   return 0;
 }
 
 int mfea_get_grip_field(mfea_handle* h, double* field, int32_t* is_set) {
   if (!h) return fail(MFEA_EINVAL, "NULL handle");
   if (!h->has_mesh) return fail(MFEA_ESTATE, "no mesh: call mfea_set_mesh first");
-  if (is_set) *is_set = h->has_field ? 1 : 0;
+  if (is_set) *is_set = h->bc.field.set ? 1 : 0;
   if (!field) return 0;
-  if (h->has_field) {
-    std::copy(h->field.begin(), h->field.end(), field);
+  if (h->bc.field.set) {
+    std::copy(h->bc.field.v.begin(), h->bc.field.v.end(), field);
     return 0;
   }
   std::fill(field, field + 3 * h->N, 0.0);
   for (const int64_t n : h->top)
-    for (int c = 0; c < 3; ++c) field[3 * n + c] = h->grip.top[c];
+    for (int c = 0; c < 3; ++c) field[3 * n + c] = h->bc.grip.top[c];
   for (const int64_t n : h->bot)
-    for (int c = 0; c < 3; ++c) field[3 * n + c] = h->grip.bot[c];
+    for (int c = 0; c < 3; ++c) field[3 * n + c] = h->bc.grip.bot[c];
   return 0;
 }
 
 int mfea_get_grip_motion(mfea_handle* h, double top[3], double bot[3]) {
   if (!h) return fail(MFEA_EINVAL, "NULL handle");
   for (int c = 0; c < 3; ++c) {
-    if (top) top[c] = h->grip.top[c];
-    if (bot) bot[c] = h->grip.bot[c];
+    if (top) top[c] = h->bc.grip.top[c];
+    if (bot) bot[c] = h->bc.grip.bot[c];
   }
   return 0;
 }
@@ -4268,26 +4268,21 @@ int mfea_get_grip_work(mfea_handle* h, double* top, double* bot) {
   HIPC(pt.gw_red.alloc(4));
   const int64_t row0[2] = {P.n_free, P.n_free + P.n_top};
   const int64_t nrows[2] = {P.n_top, P.n_nodes - P.n_ghost - P.n_free - P.n_top};
-  const double* const dir[2] = {h->grip.top, h->grip.bot};
+  const double* const dir[2] = {h->bc.grip.top, h->bc.grip.bot};
   double* const out[2] = {top, bot};
+  BcForm bc = h->bc.form(pt);
+  bc.grip = &h->bc.grip;  // (the reaction vector and its product for the tensile directions too)
   for (int b = 0; b < 2; ++b) {
     if (!out[b]) continue;
-    if (h->has_field)
-      launch_reaction_field(s, row0[b], nrows[b], P.n_nodes, pt.slice_ptr.ptr, pt.row_len.ptr, pt.s_col.ptr,
-                            pt.val.ptr, pt.diag.ptr, pt.G, pt.x.ptr, pt.partials.ptr, tix(pt, 3), pt.gw_red.ptr + 3,
-                            pt.grip_d.ptr + 3 * (row0[b] - P.n_free));
-    else
-      launch_reaction3(s, row0[b], nrows[b], P.n_nodes, pt.slice_ptr.ptr, pt.row_len.ptr, pt.s_col.ptr, pt.val.ptr,
-                       pt.diag.ptr, pt.G, pt.x.ptr, pt.partials.ptr, tix(pt, 3), pt.gw_red.ptr, dir[b],
-                       pt.gw_red.ptr + 3);
+    launch_band_force(s, pt, bc, row0[b], nrows[b], dir[b], pt.gw_red.ptr, pt.gw_red.ptr + 3);
     HIPC(hipGetLastError());
     HIPC(hmemcpy(h, out[b], pt.gw_red.ptr + 3, sizeof(double), hipMemcpyDeviceToHost));
   }
   return 0;
 }
 
-// A force vector per free node (kernels.hpp NodeLoad): it enters where the
-// grips' values enter, the five RHS sites, and a change drops what a change of
+// A force vector per free node (bc_form.hpp NodeLoad): it enters where the
+// grips' values enter, the four RHS sites, and a change drops what a change of
 // them drops (grip_changed).  The host copy is the state; the device rows are
 // gathered from it here, when the handle is built, and at every build.
 int mfea_set_node_loads(mfea_handle* h, const double* loads, int32_t mode) {
@@ -4296,36 +4291,25 @@ int mfea_set_node_loads(mfea_handle* h, const double* loads, int32_t mode) {
   if (h->world > 1 || h->nparts > 1) return fail(MFEA_ESTATE, "mfea_set_node_loads: one partition per handle");
   if (loads && mode != MFEA_LOAD_DEAD && mode != MFEA_LOAD_PROPORTIONAL)
     return fail(MFEA_EINVAL, "mfea_set_node_loads: mode must be MFEA_LOAD_DEAD or MFEA_LOAD_PROPORTIONAL");
-  const size_t n = (size_t)3 * h->N;
   std::vector<double> f;
-  if (loads) {
-    f.resize(n);
-    for (size_t k = 0; k < n; ++k) {
-      if (!std::isfinite(loads[k])) return fail(MFEA_EINVAL, "mfea_set_node_loads: every entry must be finite");
-      f[k] = loads[k] + 0.0;  // (a −0 entry is stored as 0)
-    }
-  }
-  if (h->has_loads == (loads != nullptr) &&
-      (!loads || (h->load_mode == mode && (n == 0 || std::memcmp(f.data(), h->loads.data(), n * sizeof(double)) == 0))))
-    return 0;
-  RC(set_device(h));
-  const int nd0 = lane_dofs(h);
-  if (h->stream) HIPC(hipStreamSynchronize(h->stream));
-  h->loads.swap(f);
-  h->has_loads = loads != nullptr;
-  h->load_mode = loads ? mode : MFEA_LOAD_DEAD;
+  const VecStage st = stage_node_vectors(h->bc.loads, loads, (size_t)3 * h->N, f);
+  if (st == VecStage::kNotFinite) return fail(MFEA_EINVAL, "mfea_set_node_loads: every entry must be finite");
+  if (st == VecStage::kSame && (!loads || h->bc.load_mode == mode)) return 0;
+  int nd0 = 0;
+  RC(swap_node_vectors(h, h->bc.loads, f, loads != nullptr, &nd0));
+  h->bc.load_mode = loads ? mode : MFEA_LOAD_DEAD;
   RC(grip_changed(h, nd0));
-  if (h->has_loads && !h->dirty && h->parts.size() == 1) RC(upload_loads(h, part0(h)));
+  if (h->bc.loads.set && !h->dirty && h->parts.size() == 1) RC(upload_loads(h, part0(h)));
   return 0;
 }
 
 int mfea_get_node_loads(mfea_handle* h, double* loads, int32_t* mode, int32_t* is_set) {
   if (!h) return fail(MFEA_EINVAL, "NULL handle");
   if (!h->has_mesh) return fail(MFEA_ESTATE, "no mesh: call mfea_set_mesh first");
-  if (is_set) *is_set = h->has_loads ? 1 : 0;
-  if (mode) *mode = h->load_mode;
+  if (is_set) *is_set = h->bc.loads.set ? 1 : 0;
+  if (mode) *mode = h->bc.load_mode;
   if (!loads) return 0;
-  if (h->has_loads) std::copy(h->loads.begin(), h->loads.end(), loads);
+  if (h->bc.loads.set) std::copy(h->bc.loads.v.begin(), h->bc.loads.v.end(), loads);
   else std::fill(loads, loads + 3 * h->N, 0.0);
   return 0;
 }
@@ -4341,10 +4325,10 @@ int mfea_get_load_work(mfea_handle* h, double* work) {
   if (partitioned(h)) return fail(MFEA_ESTATE, "mfea_get_load_work: one partition per handle");
   if (!h->assembled) return fail(MFEA_ESTATE, "mfea_get_load_work: no assembly since the last build");
   *work = 0.0;
-  if (!h->has_loads) return 0;
+  if (!h->bc.loads.set) return 0;
   Part& pt = part0(h);
   HIPC(pt.lw_red.alloc(1));
-  launch_load_work(h->stream, pt.P.n_free, pt.ld, h->load_dy_top, pt.x.ptr, pt.partials.ptr, tix(pt, 3),
+  launch_load_work(h->stream, pt.P.n_free, pt.ld, h->bc.load_dy_top, pt.x.ptr, pt.partials.ptr, tix(pt, 3),
                    pt.lw_red.ptr);
   HIPC(hipGetLastError());
   HIPC(hmemcpy(h, work, pt.lw_red.ptr, sizeof(double), hipMemcpyDeviceToHost));
@@ -4487,17 +4471,13 @@ int mfea_set_mesh(mfea_handle* h, int64_t n_nodes, const double* xyz, int64_t n_
   h->act_all = false;
   h->active_host.clear();
   clear_props(h);  // (indexed by the old mesh's elements)
-  if (h->has_loads) {  // (... the nodal loads by its nodes: cleared, as mfea_set_node_loads(h, NULL, 0))
+  // (... the nodal loads and the grip field by its nodes: cleared, as
+  // mfea_set_node_loads(h, NULL, 0) and mfea_set_grip_field(h, NULL))
+  for (NodeVectors* nv : {&h->bc.loads, &h->bc.field}) {
+    if (!nv->set) continue;
     if (h->stream) HIPC(hipStreamSynchronize(h->stream));
-    h->loads.clear();
-    h->has_loads = false;
-    h->load_mode = MFEA_LOAD_DEAD;
-    RC(grip_changed(h, lane_dofs(h)));
-  }
-  if (h->has_field) {  // (... the grip field by its nodes: cleared, as mfea_set_grip_field(h, NULL))
-    if (h->stream) HIPC(hipStreamSynchronize(h->stream));
-    h->field.clear();
-    h->has_field = false;
+    nv->reset();
+    if (nv == &h->bc.loads) h->bc.load_mode = MFEA_LOAD_DEAD;
     RC(grip_changed(h, lane_dofs(h)));
   }
   h->planar = true;
@@ -4592,7 +4572,7 @@ int mfea_solve(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_op
   if (!h->assembled) RC(assemble_impl(h, nullptr));
   // (nodal loads set after the assembly: no mask of K's activity yet — the
   // current one's, which is K's unless a post has moved it since)
-  if (h->has_loads && !partitioned(h) && part0(h).ld_mask_gen != h->k_from.act_gen) RC(ensure_load_mask(h));
+  if (h->bc.loads.set && !partitioned(h) && part0(h).ld_mask_gen != h->k_from.act_gen) RC(ensure_load_mask(h));
   return solve_any(h, dy_top, dy_bot, &o, st);
 }
 
@@ -4634,7 +4614,7 @@ static int step_impl(mfea_handle* h, double dy_top, double dy_bot, const mfea_so
     if (fuse_rhs && !(h->opt_amg_start && o.precond == MFEA_PC_GAMG)) {
       Part& pt = part0(h);
       launch_cg_rhs(s, sell_op(pt), pt.code.ptr, dy_top, dy_bot, o.reg, 2, cg_vecs(pt), pt.partials.ptr, tix(pt, 0),
-                    pt.red.ptr, h->grip_arg(), field_arg(h, pt), load_arg(h, pt));
+                    pt.red.ptr, h->bc.form(pt));
       HIPC(hipGetLastError());
       h->rhs_fused = true;
       h->rhs_dy[0] = dy_top;
@@ -4749,7 +4729,7 @@ int mfea_event(mfea_handle* h, double dy_top, double dy_bot, const mfea_solve_op
   RC(set_device(h));
   RC(ensure_built(h));
   if (partitioned(h)) return fail(MFEA_ESTATE, "mfea_event: one partition per handle");
-  if (h->has_loads && h->load_mode == MFEA_LOAD_DEAD) return fail(MFEA_ESTATE, kDeadLoadEvents);
+  if (h->bc.loads.set && h->bc.load_mode == MFEA_LOAD_DEAD) return fail(MFEA_ESTATE, kDeadLoadEvents);
   return event_impl(h, dy_top, dy_bot, opts, evopts, 0, out, st);
 }
 
@@ -5039,7 +5019,7 @@ int mfea_run_events(mfea_handle* h, int32_t n_events, double dy_top, double dy_b
   RC(set_device(h));
   RC(ensure_built(h));
   if (partitioned(h)) return fail(MFEA_ESTATE, "mfea_run_events: one partition per handle");
-  if (h->has_loads && h->load_mode == MFEA_LOAD_DEAD) return fail(MFEA_ESTATE, kDeadLoadEvents);
+  if (h->bc.loads.set && h->bc.load_mode == MFEA_LOAD_DEAD) return fail(MFEA_ESTATE, kDeadLoadEvents);
   Part& pt = part0(h);
   const int64_t E = pt.P.n_elems;
   if (E) HIPC(hipMemsetAsync(pt.event_of.ptr, 0xFF, E * sizeof(int32_t), h->stream));

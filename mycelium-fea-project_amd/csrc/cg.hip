@@ -66,10 +66,10 @@ __device__ __forceinline__ void store3(double* __restrict__ v, int64_t row, cons
 // Free rows: b = 0 − K_fk x_k (only the y DOF of a grip node is nonzero),
 // M⁻¹ from K_ii + reg·I, x = 0, r₀ = b, p = s = 0.  Known rows: x = (0, dy, 0),
 // every Krylov vector and M⁻¹ = 0, so gathers across the boundary read zeros.
-// GM = GripVec (kernels.hpp): known rows x = p = fl(dy · direction), and a
+// GM = GripVec (bc_form.hpp): known rows x = p = fl(dy · direction), and a
 // known neighbour's whole block, b −= V p (grip_mac).
 // GM = GripField: the same with p per known row, fl(dy of its class · its vector).
-// LD = NodeLoad (kernels.hpp): b = q − K_fk x_k, the row's load and mask byte
+// LD = NodeLoad (bc_form.hpp): b = q − K_fk x_k, the row's load and mask byte
 // fetched with its slot pointer and length.
 // ---------------------------------------------------------------------------
 template <bool BLOCK, class GM, class LD = LoadNone>
@@ -516,41 +516,24 @@ __global__ void k_cg_advance(int chunk, int shift, Slot* slots, SolveState* st, 
 }
 
 // ---------------------------------------------------------------------------
-// the grip form g and the load form ld chosen: the kernel by the preconditioner
-template <class GM, class LD>
-static void cg_rhs_launch(hipStream_t s, const SellOp& op, const uint8_t* code, double dy_top, double dy_bot,
-                          double reg, int precond, const CgVecs& v, double* partials, unsigned* ticket,
-                          double* red_out, GM g, LD ld) {
-  const dim3 grid((unsigned)grid_rows(op.N > 0 ? op.N : 1));
-  if (precond == 2)
-    hipLaunchKernelGGL((k_amg_rhs<GM, LD>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials, ticket,
-                       red_out, g, ld);
-  else if (precond == 1)
-    hipLaunchKernelGGL((k_cg_rhs<true, GM, LD>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, reg, v,
-                       partials, ticket, red_out, g, ld);
-  else
-    hipLaunchKernelGGL((k_cg_rhs<false, GM, LD>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, reg, v,
-                       partials, ticket, red_out, g, ld);
-}
-template <class LD>
-static void cg_rhs_grip(hipStream_t s, const SellOp& op, const uint8_t* code, double dy_top, double dy_bot,
-                        double reg, int precond, const CgVecs& v, double* partials, unsigned* ticket,
-                        double* red_out, const GripVec* grip, const double* field, LD ld) {
-  if (field)  // (a grip field: before the directions)
-    cg_rhs_launch(s, op, code, dy_top, dy_bot, reg, precond, v, partials, ticket, red_out, GripField{field}, ld);
-  else if (grip)  // (the directions other than the tensile test's)
-    cg_rhs_launch(s, op, code, dy_top, dy_bot, reg, precond, v, partials, ticket, red_out, *grip, ld);
-  else
-    cg_rhs_launch(s, op, code, dy_top, dy_bot, reg, precond, v, partials, ticket, red_out, GripY{}, ld);
-}
+// the grip and load forms by bc (bc_form.hpp), the kernel by the preconditioner
 void launch_cg_rhs(hipStream_t s, const SellOp& op, const uint8_t* code, double dy_top,
                    double dy_bot, double reg, int precond, const CgVecs& v, double* partials,
-                   unsigned* ticket, double* red_out, const GripVec* grip, const double* field,
-                   const NodeLoad* load) {
-  if (load)
-    cg_rhs_grip(s, op, code, dy_top, dy_bot, reg, precond, v, partials, ticket, red_out, grip, field, *load);
-  else
-    cg_rhs_grip(s, op, code, dy_top, dy_bot, reg, precond, v, partials, ticket, red_out, grip, field, LoadNone{});
+                   unsigned* ticket, double* red_out, const BcForm& bc) {
+  const dim3 grid((unsigned)grid_rows(op.N > 0 ? op.N : 1));
+  with_bc(bc, [&](auto g, auto ld) {
+    using GM = decltype(g);
+    using LD = decltype(ld);
+    if (precond == 2)
+      hipLaunchKernelGGL((k_amg_rhs<GM, LD>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, v, partials, ticket,
+                         red_out, g, ld);
+    else if (precond == 1)
+      hipLaunchKernelGGL((k_cg_rhs<true, GM, LD>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, reg, v,
+                         partials, ticket, red_out, g, ld);
+    else
+      hipLaunchKernelGGL((k_cg_rhs<false, GM, LD>), grid, dim3(kBlock), 0, s, op, code, dy_top, dy_bot, reg, v,
+                         partials, ticket, red_out, g, ld);
+  });
 }
 
 void launch_cg_init_finalize(hipStream_t s, const double* red, double rtol, double atol, int norm,

@@ -241,18 +241,13 @@ void launch_event_scan(hipStream_t s, EventScan q) {
   q.partials_e = q.partials_r + (q.vec ? 3 : 1) * (q.grid_r + kShards);  // (three sums: three times the room)
   q.pmax = q.partials_e + (q.grid_e + kShards);
   const dim3 g(q.grid_r + q.grid_e);
-  if (q.field) {
-    if (q.strength) hipLaunchKernelGGL((k_event_scan<true, GripField>), g, dim3(kBlock), 0, s, q);
-    else hipLaunchKernelGGL((k_event_scan<false, GripField>), g, dim3(kBlock), 0, s, q);
-    return;
-  }
-  if (q.vec) {
-    if (q.strength) hipLaunchKernelGGL((k_event_scan<true, GripVec>), g, dim3(kBlock), 0, s, q);
-    else hipLaunchKernelGGL((k_event_scan<false, GripVec>), g, dim3(kBlock), 0, s, q);
-    return;
-  }
-  if (q.strength) hipLaunchKernelGGL((k_event_scan<true, GripY>), g, dim3(kBlock), 0, s, q);
-  else hipLaunchKernelGGL((k_event_scan<false, GripY>), g, dim3(kBlock), 0, s, q);
+  // (only the form's type is read: the kernel takes w and the field from q)
+  const GripVec vec{};
+  with_grip(BcForm{q.vec ? &vec : nullptr, q.field, nullptr}, [&](auto gm) {
+    using GM = decltype(gm);
+    if (q.strength) hipLaunchKernelGGL((k_event_scan<true, GM>), g, dim3(kBlock), 0, s, q);
+    else hipLaunchKernelGGL((k_event_scan<false, GM>), g, dim3(kBlock), 0, s, q);
+  });
 }
 
 int64_t event_scan_partials(int64_t n_top, int64_t n_elems, bool vec) {

@@ -328,111 +328,6 @@ __global__ __launch_bounds__(kBlock) void k_assemble(int64_t N, const double* __
   }
 }
 
-// ---------------------------------------------------------------------------
-// Dirichlet elimination + PCG start (src/fea_solver.py:115-125;
-// src/fea_petsc.cpp:286-320).  Free rows: b_i = −Σ_{known j} K_ij x_j,
-// x=0, r=b, z=M⁻¹b, p=z.  Known rows: x = prescribed (0, dy, 0), p = 0 so the
-// free-row SpMV sees K_fk·p = 0.  Reduces (r·z, b·b, z·z).
-// ---------------------------------------------------------------------------
-
-// LD = NodeLoad: b = q − K_fk x_k (kernels.hpp), fetched with the row's first loads
-template <class GM, class LD = LoadNone>
-__global__ __launch_bounds__(kBlock) void k_rhs_init(
-    int64_t N, int64_t nf, const int32_t* __restrict__ slice_ptr, const int32_t* __restrict__ row_len,
-    const int32_t* __restrict__ s_col, const double* __restrict__ val, const double* __restrict__ diag,
-    int64_t G, const uint8_t* __restrict__ code, double dy_top, double dy_bot, double reg,
-    int precond, double* __restrict__ x, double* __restrict__ r, double* __restrict__ p,
-    double* __restrict__ dinv, double* partials, unsigned* ticket, double* red_out, GM g, LD ld) {
-  const int64_t row = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  double acc[3] = {0.0, 0.0, 0.0};  // r·z, b·b, z·z
-  constexpr bool VEC = std::is_same<GM, GripVec>::value;
-  constexpr bool FLD = std::is_same<GM, GripField>::value;
-  GripP gp{};
-  if constexpr (VEC) gp = grip_disp(g, dy_top, dy_bot);
-  if (row < nf) {
-    const int64_t base = (int64_t)slice_ptr[row >> 6] * 64 + (row & 63);
-    const int len = row_len[row];
-    const LoadRow<LD> lr = load_fetch(ld, row);
-    double kx = 0.0, ky = 0.0, kz = 0.0;  // (K_fk · x_k) for this row
-    for (int k = 0; k < len; ++k) {
-      const int64_t idx = base + (int64_t)k * 64;
-      const int32_t j = s_col[idx];
-      if (j >= nf) {
-        if constexpr (VEC) {  // the whole block: b −= V p
-          double v[6], pk[3], k3[3] = {kx, ky, kz};
-#pragma unroll
-          for (int c = 0; c < 6; ++c) v[c] = val[(int64_t)c * G + idx];
-          grip_of(gp, code[j], pk);
-          grip_mac(v, pk, k3);
-          kx = k3[0];
-          ky = k3[1];
-          kz = k3[2];
-        } else if constexpr (FLD) {  // ... with p of this neighbour
-          double v[6], pk[3], k3[3] = {kx, ky, kz};
-#pragma unroll
-          for (int c = 0; c < 6; ++c) v[c] = val[(int64_t)c * G + idx];
-          grip_of(g, j, nf, code[j], dy_top, dy_bot, pk);
-          grip_mac(v, pk, k3);
-          kx = k3[0];
-          ky = k3[1];
-          kz = k3[2];
-        } else {
-          const double dy = code[j] == 2 ? dy_bot : dy_top;  // only the y DOF is nonzero
-          kx = fma(val[1 * G + idx], dy, kx);
-          ky = fma(val[3 * G + idx], dy, ky);
-          kz = fma(val[4 * G + idx], dy, kz);
-        }
-      }
-    }
-    const double kf[3] = {kx, ky, kz};
-    double b[3];
-    load_rhs(ld, lr, dy_top, kf, b);  // F_f = 0 − K_fk x_k (py:122), or q − K_fk x_k
-    double A[6];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) A[c] = diag[(int64_t)c * N + row];
-    A[0] += reg; A[3] += reg; A[5] += reg;                // K_ff + reg·I (py:125)
-    double z[3];
-    if (precond == 1) {
-      double B[6];
-      sym_inverse(A, B);
-#pragma unroll
-      for (int c = 0; c < 6; ++c) dinv[6 * row + c] = B[c];
-      sym_apply(B, b, z);
-    } else {
-      const double d0 = 1.0 / A[0], d1 = 1.0 / A[3], d2 = 1.0 / A[5];
-      dinv[3 * row] = d0; dinv[3 * row + 1] = d1; dinv[3 * row + 2] = d2;
-      z[0] = d0 * b[0]; z[1] = d1 * b[1]; z[2] = d2 * b[2];
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      x[3 * row + a] = 0.0;
-      r[3 * row + a] = b[a];
-      p[3 * row + a] = z[a];
-      acc[0] = fma(b[a], z[a], acc[0]);
-      acc[1] = fma(b[a], b[a], acc[1]);
-      acc[2] = fma(z[a], z[a], acc[2]);
-    }
-  } else if (row < N) {
-    if constexpr (VEC) {
-      double xk[3];
-      grip_of(gp, code[row], xk);
-#pragma unroll
-      for (int a = 0; a < 3; ++a) x[3 * row + a] = xk[a];
-    } else if constexpr (FLD) {
-      double xk[3];
-      grip_of(g, row, nf, code[row], dy_top, dy_bot, xk);
-#pragma unroll
-      for (int a = 0; a < 3; ++a) x[3 * row + a] = xk[a];
-    } else {
-      x[3 * row] = 0.0;
-      x[3 * row + 1] = code[row] == 2 ? dy_bot : dy_top;
-      x[3 * row + 2] = 0.0;
-    }
-    p[3 * row] = 0.0; p[3 * row + 1] = 0.0; p[3 * row + 2] = 0.0;
-  }
-  block_publish<3>(acc, partials, ticket, red_out);
-}
-
 __global__ void k_init_finalize(const double* red, double rtol, double atol, int norm, int max_it,
                                 double reg, Slot* slots, SolveState* st) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -462,48 +357,6 @@ __device__ __forceinline__ bool run_iter(const Slot* slots, const SolveState* st
   const Slot& s = slots[j];
   const double res = st->norm == 1 ? s.v[3] : s.v[2];
   return s.flag == kRun && res > st->tol2 && (st->base + j) < st->max_it;
-}
-
-// ---------------------------------------------------------------------------
-// SpMV  q = (K_ff + reg·I) p  over the free rows, fused with the partial p·q.
-// SELL-64: lane l of the wave owning slice s handles row 64 s + l; slot k of
-// that row sits at (slice_ptr[s] + k)·64 + l, so every column/value load of a
-// wave is one contiguous 256/512-byte transaction.  p is gathered per
-// neighbour (24 B, L2/MALL-resident for meshes up to ~10 M DOF).
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void k_spmv_sell(
-    int j, int64_t nf, int64_t N, const int32_t* __restrict__ slice_ptr,
-    const int32_t* __restrict__ row_len, const int32_t* __restrict__ s_col,
-    const double* __restrict__ val, const double* __restrict__ diag, int64_t G,
-    const double* __restrict__ p, double* __restrict__ q, Slot* slots, const SolveState* st,
-    double* partials, unsigned* ticket) {
-  if (!run_iter(slots, st, j)) return;
-  const int64_t row = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  double pq[1] = {0.0};
-  if (row < nf) {
-    const double reg = st->reg;
-    const int64_t base = (int64_t)slice_ptr[row >> 6] * 64 + (row & 63);
-    const int len = row_len[row];
-    const double p0 = p[3 * row], p1 = p[3 * row + 1], p2 = p[3 * row + 2];
-    const double d0 = diag[row], d1 = diag[N + row], d2 = diag[2 * N + row],
-                 d3 = diag[3 * N + row], d4 = diag[4 * N + row], d5 = diag[5 * N + row];
-    double y0 = fma(d0 + reg, p0, fma(d1, p1, d2 * p2));
-    double y1 = fma(d1, p0, fma(d3 + reg, p1, d4 * p2));
-    double y2 = fma(d2, p0, fma(d4, p1, (d5 + reg) * p2));
-    for (int k = 0; k < len; ++k) {
-      const int64_t idx = base + (int64_t)k * 64;
-      const int64_t c = s_col[idx];
-      const double v0 = val[idx], v1 = val[G + idx], v2 = val[2 * G + idx],
-                   v3 = val[3 * G + idx], v4 = val[4 * G + idx], v5 = val[5 * G + idx];
-      const double q0 = p[3 * c], q1 = p[3 * c + 1], q2 = p[3 * c + 2];
-      y0 = fma(v0, q0, fma(v1, q1, fma(v2, q2, y0)));
-      y1 = fma(v1, q0, fma(v3, q1, fma(v4, q2, y1)));
-      y2 = fma(v2, q0, fma(v4, q1, fma(v5, q2, y2)));
-    }
-    q[3 * row] = y0; q[3 * row + 1] = y1; q[3 * row + 2] = y2;
-    pq[0] = fma(p0, y0, fma(p1, y1, p2 * y2));
-  }
-  block_publish<1>(pq, partials, ticket, &slots[j].v[0]);
 }
 
 // ---------------------------------------------------------------------------
@@ -1046,51 +899,32 @@ __global__ __launch_bounds__(kBlock) void k_spmv_csr(int j, int64_t n, const int
 // ---------------------------------------------------------------------------
 #define MFEA_GRID(n) dim3((unsigned)(n)), dim3(kBlock), 0, s
 
-// the RHS form of the row gather: the material form m, the grip form and the
-// load form by the arguments
-template <class M, class LD>
-static void assemble_rhs_launch(hipStream_t s, int64_t N, const double* xyz, const int32_t* slice_ptr,
-                                const int32_t* row_len, const int32_t* s_col, const int32_t* s_elem,
-                                const uint8_t* active, M m, int64_t G, double* val, double* diag,
-                                const AsmRhs& rhs) {
-  if (rhs.field)
-    hipLaunchKernelGGL((k_assemble<true, M, GripField, LD>), MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, xyz,
-                       slice_ptr, row_len, s_col, s_elem, active, m, G, val, diag, rhs);
-  else if (rhs.vec)
-    hipLaunchKernelGGL((k_assemble<true, M, GripVec, LD>), MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, xyz, slice_ptr,
-                       row_len, s_col, s_elem, active, m, G, val, diag, rhs);
-  else
-    hipLaunchKernelGGL((k_assemble<true, M, GripY, LD>), MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, xyz, slice_ptr,
-                       row_len, s_col, s_elem, active, m, G, val, diag, rhs);
+// f(m) or f(ElemSection{sec}): the material form by the per-element array
+template <class F>
+static void with_material(Material m, const double2* sec, F&& f) {
+  if (sec) f(ElemSection{sec});
+  else f(m);
 }
 
 void launch_assemble(hipStream_t s, int64_t N, const double* xyz, const int32_t* slice_ptr,
                      const int32_t* row_len, const int32_t* s_col, const int32_t* s_elem,
                      const uint8_t* active, Material m, int64_t G, double* val, double* diag,
                      const AsmRhs* rhs, const double2* sec) {
-  const ElemSection ms{sec};
-  if (rhs) {  // (the reduction's blocks publish even when N = 0)
-    if (rhs->load.f && sec)
-      assemble_rhs_launch<ElemSection, NodeLoad>(s, N, xyz, slice_ptr, row_len, s_col, s_elem, active, ms, G, val,
-                                                 diag, *rhs);
-    else if (rhs->load.f)
-      assemble_rhs_launch<Material, NodeLoad>(s, N, xyz, slice_ptr, row_len, s_col, s_elem, active, m, G, val, diag,
-                                              *rhs);
-    else if (sec)
-      assemble_rhs_launch<ElemSection, LoadNone>(s, N, xyz, slice_ptr, row_len, s_col, s_elem, active, ms, G, val,
-                                                 diag, *rhs);
-    else
-      assemble_rhs_launch<Material, LoadNone>(s, N, xyz, slice_ptr, row_len, s_col, s_elem, active, m, G, val, diag,
-                                              *rhs);
-    return;
-  }
-  if (N <= 0) return;
-  if (sec)
-    hipLaunchKernelGGL((k_assemble<false, ElemSection>), MFEA_GRID(grid_rows(N)), N, xyz, slice_ptr, row_len, s_col,
-                       s_elem, active, ms, G, val, diag, AsmRhs{});
-  else
-    hipLaunchKernelGGL((k_assemble<false, Material>), MFEA_GRID(grid_rows(N)), N, xyz, slice_ptr, row_len, s_col,
-                       s_elem, active, m, G, val, diag, AsmRhs{});
+  if (!rhs && N <= 0) return;  // (the RHS form's blocks publish their reduction even when N = 0)
+  with_material(m, sec, [&](auto mm) {
+    using M = decltype(mm);
+    if (!rhs) {
+      hipLaunchKernelGGL((k_assemble<false, M>), MFEA_GRID(grid_rows(N)), N, xyz, slice_ptr, row_len, s_col, s_elem,
+                         active, mm, G, val, diag, AsmRhs{});
+      return;
+    }
+    // the RHS form of the row gather: the grip and load forms by the fields of rhs
+    const BcForm bc{rhs->vec ? &rhs->grip : nullptr, rhs->field, rhs->load.f ? &rhs->load : nullptr};
+    with_bc(bc, [&](auto g, auto ld) {
+      hipLaunchKernelGGL((k_assemble<true, M, decltype(g), decltype(ld)>), MFEA_GRID(grid_rows(N > 0 ? N : 1)), N,
+                         xyz, slice_ptr, row_len, s_col, s_elem, active, mm, G, val, diag, *rhs);
+    });
+  });
 }
 
 void launch_assemble_colour(hipStream_t s, int colors, const int32_t* cstart, const int32_t* entry,
@@ -1120,51 +954,10 @@ void launch_assemble_elems(hipStream_t s, int64_t E, int64_t N, const int32_t* e
   if (N > 0) hipLaunchKernelGGL(k_diag_rows, MFEA_GRID(grid_rows(N)), N, slice_ptr, row_len, G, val, diag);
 }
 
-template <class LD>
-static void rhs_init_launch(hipStream_t s, int64_t N, int64_t nf, const int32_t* slice_ptr, const int32_t* row_len,
-                            const int32_t* s_col, const double* val, const double* diag, int64_t G,
-                            const uint8_t* code, double dy_top, double dy_bot, double reg, int precond, double* x,
-                            double* r, double* p, double* dinv, double* partials, unsigned* ticket, double* red_out,
-                            const GripVec* grip, const double* field, LD ld) {
-  if (field)
-    hipLaunchKernelGGL((k_rhs_init<GripField, LD>), MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, nf, slice_ptr, row_len,
-                       s_col, val, diag, G, code, dy_top, dy_bot, reg, precond, x, r, p, dinv, partials, ticket,
-                       red_out, GripField{field}, ld);
-  else if (grip)
-    hipLaunchKernelGGL((k_rhs_init<GripVec, LD>), MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, nf, slice_ptr, row_len,
-                       s_col, val, diag, G, code, dy_top, dy_bot, reg, precond, x, r, p, dinv, partials, ticket,
-                       red_out, *grip, ld);
-  else
-    hipLaunchKernelGGL((k_rhs_init<GripY, LD>), MFEA_GRID(grid_rows(N > 0 ? N : 1)), N, nf, slice_ptr, row_len,
-                       s_col, val, diag, G, code, dy_top, dy_bot, reg, precond, x, r, p, dinv, partials, ticket,
-                       red_out, GripY{}, ld);
-}
-void launch_rhs_init(hipStream_t s, int64_t N, int64_t nf, const int32_t* slice_ptr,
-                     const int32_t* row_len, const int32_t* s_col, const double* val,
-                     const double* diag, int64_t G, const uint8_t* code, double dy_top,
-                     double dy_bot, double reg, int precond, double* x, double* r, double* p,
-                     double* dinv, double* partials, unsigned* ticket, double* red_out, const GripVec* grip,
-                     const double* field, const NodeLoad* load) {
-  if (load)
-    rhs_init_launch(s, N, nf, slice_ptr, row_len, s_col, val, diag, G, code, dy_top, dy_bot, reg, precond, x, r, p,
-                    dinv, partials, ticket, red_out, grip, field, *load);
-  else
-    rhs_init_launch(s, N, nf, slice_ptr, row_len, s_col, val, diag, G, code, dy_top, dy_bot, reg, precond, x, r, p,
-                    dinv, partials, ticket, red_out, grip, field, LoadNone{});
-}
-
 void launch_init_finalize(hipStream_t s, const double* red, double rtol, double atol, int norm,
                           int max_it, double reg, Slot* slots, SolveState* st) {
   hipLaunchKernelGGL(k_init_finalize, dim3(1), dim3(64), 0, s, red, rtol, atol, norm, max_it, reg,
                      slots, st);
-}
-
-void launch_spmv_sell(hipStream_t s, int j, int64_t nf, int64_t N, const int32_t* slice_ptr,
-                      const int32_t* row_len, const int32_t* s_col, const double* val,
-                      const double* diag, int64_t G, const double* p, double* q, Slot* slots,
-                      const SolveState* st, double* partials, unsigned* ticket) {
-  hipLaunchKernelGGL(k_spmv_sell, MFEA_GRID(grid_rows(nf > 0 ? nf : 1)), j, nf, N, slice_ptr,
-                     row_len, s_col, val, diag, G, p, q, slots, st, partials, ticket);
 }
 
 void launch_update(hipStream_t s, int j, int64_t n, int precond, double* x, double* r,

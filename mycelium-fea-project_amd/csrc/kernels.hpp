@@ -14,6 +14,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bc_form.hpp"
+
 namespace mfea {
 
 constexpr int kBlock = 256;  // 4 wavefronts
@@ -94,47 +96,9 @@ struct ElemPost {
   const double* strength;
 };
 
-// Grip motion (mfea_set_grip_motion): the prescribed displacement of a grip
-// node is amplitude · direction, p[c] = fl(dy · dir[c]) — one f64 product per
-// component, formed once per launch (device_util.hpp grip_disp).  GripY: the
-// tensile test, (0, dy, 0) — the kernels as they were before the directions
-// existed.  GripVec: any two directions; a free row's RHS then takes the whole
-// symmetric block of a known neighbour, b −= V·p, and a known row x = p.  The
-// kernels are templates over the two (no run-time choice inside them); a
-// launcher picks GripVec when its `grip` argument is non-null.
-// GripField (mfea_set_grip_field): a vector per grip node instead of one per
-// band — d holds 3 doubles per known row in Pattern row order, row j at
-// d[3·(j − nf)], and the prescribed displacement of row j is
-// p[c] = fl(amp · d[3·(j − nf) + c]) with amp the amplitude of the row's class
-// (dy_bot for a bottom row, dy_top for a top row).  The RHS term and the known
-// rows' x are GripVec's with p per row.  A launcher picks GripField when its
-// `field` argument is non-null, before it looks at `grip`.
-struct GripY {};
-struct GripVec {
-  double top[3], bot[3];
-};
-struct GripField {
-  const double* d;
-};
-
-// Nodal loads (mfea_set_node_loads): the load policy beside the grip policy.
-// LoadNone: b = 0 − K_fk x_k, the kernels as they were before loads existed.
-// NodeLoad: a free row r takes b[c] = q[c] − k[c], k the grip term accumulated
-// as without loads and
-//   q[c] = fl(amp · f[3r + c]) + 0,  amp = dy_top (prop) or 1 (a dead load:
-//   the product is the stored value), 0 where fl[r] is set
-// f: 3 doubles per free row in Pattern row order; fl: a byte per free row, 1 on
-// the rows of floating pieces (launch_floating's mask in row order) — their
-// load is dropped, so they stay at exactly zero.  (+ 0: a product −0 counts as
-// 0, as a stored −0 does; with f = 0 the bits are LoadNone's.)  The kernels are
-// templates over the two; a launcher picks NodeLoad when its `load` argument is
-// non-null.
-struct LoadNone {};
-struct NodeLoad {
-  const double* f;
-  const uint8_t* fl;
-  int32_t prop;
-};
+// The grip forms (GripY / GripVec / GripField) and the load forms (LoadNone /
+// NodeLoad) the RHS, reaction and event kernels are templates over, and the
+// BcForm a launcher chooses them by: bc_form.hpp.
 
 // ---- launchers (defined in kernels.hip) -------------------------------------
 // The GAMG solves' RHS formed in the assembly's row pass (k_amg_rhs's work:
@@ -181,21 +145,8 @@ void launch_assemble_elems(hipStream_t s, int64_t E, int64_t N, const int32_t* e
                            const int32_t* row_len, int64_t G, double* val, double* diag,
                            const double2* sec = nullptr);
 
-void launch_rhs_init(hipStream_t s, int64_t N, int64_t nf, const int32_t* slice_ptr,
-                     const int32_t* row_len, const int32_t* s_col, const double* val,
-                     const double* diag, int64_t G, const uint8_t* code, double dy_top,
-                     double dy_bot, double reg, int precond, double* x, double* r, double* p,
-                     double* dinv, double* partials, unsigned* ticket, double* red_out,
-                     const GripVec* grip = nullptr, const double* field = nullptr,
-                     const NodeLoad* load = nullptr);
-
 void launch_init_finalize(hipStream_t s, const double* red, double rtol, double atol, int norm,
                           int max_it, double reg, Slot* slots, SolveState* st);
-
-void launch_spmv_sell(hipStream_t s, int j, int64_t nf, int64_t N, const int32_t* slice_ptr,
-                      const int32_t* row_len, const int32_t* s_col, const double* val,
-                      const double* diag, int64_t G, const double* p, double* q, Slot* slots,
-                      const SolveState* st, double* partials, unsigned* ticket);
 
 void launch_update(hipStream_t s, int j, int64_t n, int precond, double* x, double* r,
                    const double* p, const double* q, const double* dinv, Slot* slots,
@@ -363,11 +314,11 @@ void launch_spmv_csr(hipStream_t s, int j, int64_t n, const int64_t* indptr,
 // ---- single-reduction CG on the SELL operator (one kernel per iteration) ----
 // k_cg_rhs: b, M⁻¹, x, r₀ = b, p = s = w = 0; reduces (b·b, u₀·u₀) into red[0..1].
 // precond 0 Jacobi, 1 block Jacobi, 2 the GAMG solves (k_amg_rhs: b and the
-// known rows' x only, u₀·u₀ = 0).
+// known rows' x only, u₀·u₀ = 0).  bc: the grip and load forms (bc_form.hpp
+// with_bc picks the instantiation; the default: GripY, LoadNone).
 void launch_cg_rhs(hipStream_t s, const SellOp& op, const uint8_t* code, double dy_top,
                    double dy_bot, double reg, int precond, const CgVecs& v, double* partials,
-                   unsigned* ticket, double* red_out, const GripVec* grip = nullptr,
-                   const double* field = nullptr, const NodeLoad* load = nullptr);
+                   unsigned* ticket, double* red_out, const BcForm& bc = BcForm{});
 // part: 2 parity buffers × [4][kCgMaxPartials] block partials (cg.hip)
 constexpr int kCgMaxPartials = 512;
 // k_cg_first: w₀ = A u₀; block partials (γ₀, δ₀, r·r, u·u) → part parity 0;
